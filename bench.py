@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — images/sec of OMG's stage-2 denoising call on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One "step" = one batch of `--images-per-step` (default 8) independent requests, each a complete stage-2 call of the
@@ -21,6 +21,11 @@ timed in an instrumented pass of one plain + one fused denoising step) and "cpu_
 the host cores, bounded sample, extrapolated).  "value" is the reference's as-executed work (336 sample-forwards per
 image); "value_dedup" is the same images with the exactly redundant sample-forwards of steps 0..15 executed once
 (bitwise the same latents, tests/test_pipeline_gpu.py), timed in a second, shorter region.
+
+`--dump-outputs DIR` writes what the last timed step computed (rank 0's requests) as DIR/<name>.npy in float32: `latents` (requests, 2 samples,
+4, h, w) and `images` (decoded images, requests x 2 samples x 3 x H x W; absent with --no-vae).  An output of more than 2^21 values is
+written as a fixed, seeded sample instead: `<name>_sample` (the values) and `<name>_sample_index` (their flat indices, float64).
+The inputs and weights are seeded: with the same arguments two runs compute the same things, so two builds compare output for output.
 
 `python bench.py --gpus N` without a torch.distributed environment re-launches itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` (one rank per GPU).
@@ -134,8 +139,8 @@ class PowerSampler:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3, help="images timed per GPU")
-    ap.add_argument("--warmup", type=int, default=1, help="untimed warm-up images per GPU")
+    ap.add_argument("--steps", type=int, default=3, help="timed steps per GPU (each --images-per-step requests)")
+    ap.add_argument("--warmup", type=int, default=1, help="untimed warm-up steps per GPU")
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "bf16", "fp8"],
                     help="fp8 = BASELINE configs[4]'s arithmetic: the transformer Linear layers on the MX-fp8 MFMA (omg_gemm_mx8), "
                          "everything else fp16 as in the default mode; NOT the headline configuration")
@@ -162,7 +167,11 @@ def main():
                          "the ranks and one all_gather per step exchanges the noise predictions (omg_amd.parallel.ConceptShard)")
     ap.add_argument("--config3", action="store_true",
                     help="BASELINE configs[3]'s own shape: batch 32 over 8 GPUs = 4 requests per GPU and step (--images-per-step 4); the default 8 is the throughput optimum")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the last timed step's latents and decoded images to DIR/<name>.npy "
+                    "(float32; outputs above 2^21 values as a fixed, seeded sample)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.config3:
         args.images_per_step = 4
 
@@ -226,8 +235,9 @@ def main():
             reqs.append(r)
         inputs.append(reqs)
 
-    def run_step(reqs, dedup=False):
-        """One bench step = `ips` complete stage-2 calls (independent requests batched through the UNet in lock-step)."""
+    def run_step(reqs, dedup=False, keep=None):
+        """One bench step = `ips` complete stage-2 calls (independent requests batched through the UNet in lock-step).
+        `keep`: a list that receives every decoded image pair (--dump-outputs)."""
         ctl.reset()                                                                   # inference_lora.py:274
         lat = pipe.generate_many(reqs, height=HW, width=HW, num_inference_steps=args.denoise_steps, guidance_scale=7.5,
                                  cross_attention_kwargs={"scale": 0.8}, controller=ctl, concept_models=concept, stage=2,
@@ -236,6 +246,8 @@ def main():
         if vae is not None:                                                           # both images of every request, two at a time
             for j in (range(lat.shape[0]) if not by_concept else parallel.shard_indices(lat.shape[0], rank, world)):      # concept: the decodes are split too
                 img = vae.decode_latents(lat[j])
+                if keep is not None:
+                    keep.append(img)
             assert img.shape[-1] == lat.shape[-1] * 2 ** (len(vae.config.block_out_channels) - 1)
         return lat
 
@@ -252,9 +264,10 @@ def main():
     torch.cuda.synchronize()
     if sampler is not None:
         sampler.__enter__()
+    kept = []                                                                                    # --dump-outputs: the last step's images
     t0 = time.perf_counter()
     for i in range(args.warmup, n_steps):
-        lat = run_step(inputs[i])
+        lat = run_step(inputs[i], keep=kept if args.dump_outputs and i == n_steps - 1 else None)
         allimg = gather(lat)                                                                     # the deliverable is images[1]
     torch.cuda.synchronize()
     parallel.barrier()
@@ -263,6 +276,9 @@ def main():
     if sampler is not None:
         sampler.__exit__()
     assert torch.isfinite(allimg).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"latents": lat, "images": torch.stack(kept) if kept else None})
+    del kept
     job_images = ips if by_concept else world * ips          # concept: ONE batch is split over the ranks (strong scaling)
     value = job_images * args.steps / el
 
@@ -430,6 +446,26 @@ def main():
     if torch.distributed.is_available() and torch.distributed.is_initialized():
         parallel.barrier()     # orderly shutdown: the other ranks wait for rank 0's instrumented passes, then RCCL is torn down
         torch.distributed.destroy_process_group()
+
+
+DUMP_MAX_VALUES = 1 << 21       # per output: 8 MB of float32 whole, or a sample of this many values + their float64 indices (<= 48 MB for two)
+
+
+def dump_outputs(dirname, outputs):
+    """--dump-outputs: every output as DIR/<name>.npy in float32; one of more than DUMP_MAX_VALUES values as a fixed, seeded sample
+    (the same flat indices for the same shape) in <name>_sample.npy, with the indices in <name>_sample_index.npy (float64, exact)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in outputs.items():
+        if t is None:
+            continue
+        flat = t.detach().reshape(-1)
+        if flat.numel() <= DUMP_MAX_VALUES:
+            np.save(os.path.join(dirname, f"{name}.npy"), t.detach().float().cpu().numpy())
+            continue
+        idx = torch.randint(flat.numel(), (DUMP_MAX_VALUES,), generator=torch.Generator().manual_seed(0)).sort().values
+        np.save(os.path.join(dirname, f"{name}_sample.npy"), flat[idx.to(flat.device)].float().cpu().numpy())
+        np.save(os.path.join(dirname, f"{name}_sample_index.npy"), idx.double().numpy())
 
 
 def _quiet(fn, *a):

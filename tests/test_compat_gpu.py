@@ -1,5 +1,5 @@
 """B3 (-m gpu): the reference's own driver code — ``build_model_sd`` and ``sample_image`` of inference_lora.py (:152-171, :37-73),
-transcribed verbatim (tests/test_compat_verbatim.py compares the syntax trees with /root/reference where it exists) under the script's
+transcribed verbatim (tests/test_compat_verbatim.py compares the syntax trees with the reference's, recorded in tests/golden/compat_verbatim.json) under the script's
 ORIGINAL import lines (``omg_amd.compat.install()`` registers ``src.pipelines.*``, ``src.prompt_attention.p2p_attention`` and
 ``diffusers``) — runs against omg_amd.compat on a synthetic model directory, stage 1 and stage 2,
 with and without a style LoRA and a spatial condition; the result equals the lower-level embeddings-in / latents-out API fed with the

@@ -1,6 +1,6 @@
 """B3 for the SECOND script BASELINE's north_star names (-m gpu): ``sample_image`` (:72-110), ``build_model_sd`` (:186-232),
 ``prepare_text`` (:234-255) and the two-stage main flow (:296-366) of the reference's inference_instantid.py, transcribed verbatim
-(tests/test_compat_verbatim.py compares the syntax trees with /root/reference where it exists) under the script's ORIGINAL import lines
+(tests/test_compat_verbatim.py compares the syntax trees with the reference's, recorded in tests/golden/compat_verbatim.json) under the script's ORIGINAL import lines
 (``omg_amd.compat.install()``), run against omg_amd.compat on a synthetic model directory: stage 1 (``image=None`` => no IdentityNet,
 instantid_pipeline.py:393, :426-428) and stage 2 (key-point image on every concept pass, face embeddings through
 ``concept_models._encode_prompt_image_emb``, :378-388), with and without ``pipe.controlnet2`` + ``t2i_image`` (:574-616).

@@ -4,6 +4,7 @@ import ast
 import os
 import re
 import subprocess
+import sys
 
 import pytest
 import torch
@@ -98,6 +99,34 @@ def test_bench_power_sampler_parses_rocm_smi_json():
     s.rows = [{"sclk": 1600.0, "w": 1400.0, "cap": 1400.0}, {"sclk": 1700.0, "w": 1390.0}]
     out = s.summary()
     assert out["avg_sclk_mhz"] == 1650.0 and out["avg_w"] == 1395.0 and out["cap_w"] == 1400.0 and out["samples"] == 2
+
+
+def test_bench_dump_outputs_are_float_seeded_and_bounded(tmp_path):
+    """bench.py --dump-outputs: float32 / float64 .npy files, at most 64 MB, a large output as the same seeded sample every time."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("omg_bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(0)
+    outs = {"latents": torch.randn(8, 2, 4, 128, 128, generator=g), "images": torch.rand(2, 2, 3, 512, 768, generator=g), "absent": None}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), outs)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["images_sample.npy", "images_sample_index.npy", "latents.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 << 20
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+    assert np.array_equal(np.load(tmp_path / "a" / "latents.npy"), outs["latents"].numpy())
+    idx = np.load(tmp_path / "a" / "images_sample_index.npy").astype(np.int64)
+    assert len(idx) == bench.DUMP_MAX_VALUES and idx.min() >= 0 and idx.max() < outs["images"].numel()
+    assert np.array_equal(np.load(tmp_path / "a" / "images_sample.npy"), outs["images"].reshape(-1).numpy()[idx])
+
+
+def test_bench_rejects_fewer_than_one_timed_step():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--steps" in r.stderr, r.stderr
 
 
 def test_groupnorm_workspace_holds_partials_and_folded_statistics():
