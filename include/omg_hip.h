@@ -351,6 +351,15 @@ typedef struct {
 
 int omg_fuse_cfg_step(const omg_step_args* a, void* stream);
 
+/* omg_fuse_cfg_step_ms — the same fusion + CFG + next model input with a MULTISTEP scheduler update (DPM-Solver++,
+ * omg_amd/schedulers.py DPMSolverMultistepScheduler).  a->coef is not read; instead
+ * ms_coef : device table [n_steps][8] = {a, b, cx, cm, cp, cin_next, unused, unused}; row = *a->step_idx
+ *             m = a*latents + b*eps                       (data prediction)
+ *             latents' = cx*latents + cm*m + cp*m_prev ; model_input' = cin_next * latents'
+ * x0_hist : fp32 [2,C,H,W] per request: m_prev of both samples on entry, this step's m on return.  Rows with cp == 0
+ *           (order 1: the first step) do not read it, so it needs no initialisation. */
+int omg_fuse_cfg_step_ms(const omg_step_args* a, const float* ms_coef, float* x0_hist, void* stream);
+
 /* out[0:n] = table[*step_idx * n : (*step_idx + 1) * n]: per-step conditioning (time/text embedding rows, hoisted out
  * of the loop by the host) selected with the DEVICE step counter, so a captured step graph has no host argument. */
 int omg_gather_step(int dtype, const void* table, const int32_t* step_idx, void* out, int64_t n_per_step, void* stream);

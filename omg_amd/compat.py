@@ -25,6 +25,7 @@ slots of a common :class:`omg_amd.lora.LoraBank`.
 """
 from __future__ import annotations
 
+import functools
 import json
 import os
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -40,7 +41,7 @@ from .lora import LoraBank
 from .pipeline import (ConceptModels, InstantidMultiConceptPipeline as _InstantidPipe, LoraMultiConceptPipeline as _LoraPipe,
                        StableDiffusionXLPipelineOutput)
 from .resampler import Resampler
-from .schedulers import DDIMScheduler, EulerDiscreteScheduler
+from .schedulers import DDIMScheduler, DPMSolverMultistepScheduler, EulerDiscreteScheduler
 from .text_encoder import ClipTextConfig, ClipTextEncoder, make_encode_prompt
 from .unet import UNet2DConditionModel, UNetConfig
 from .vae import AutoencoderKLDecoder, VaeConfig
@@ -115,8 +116,11 @@ class _Components:
         t2 = os.path.join(path, "tokenizer_2")
         self.tokenizer_2 = CLIPTokenizer.from_pretrained(t2) if os.path.isdir(t2) else self.tokenizer
         sched = os.path.join(path, "scheduler", "scheduler_config.json")
-        name = _json(sched).get("_class_name", "EulerDiscreteScheduler") if os.path.exists(sched) else "EulerDiscreteScheduler"
+        sched_cfg = _json(sched) if os.path.exists(sched) else {}
+        name = sched_cfg.get("_class_name", "EulerDiscreteScheduler")
         self.scheduler_class = DDIMScheduler if "DDIM" in name else EulerDiscreteScheduler     # SDXL-base ships EulerDiscrete
+        if name == "DPMSolverMultistepScheduler":       # built from the file's keys (an unsupported option raises here)
+            self.scheduler_class = functools.partial(DPMSolverMultistepScheduler.from_config, sched_cfg)
         self.bank = LoraBank(self.unet, [])
 
     def _text_encoder(self, sub: str, with_projection: bool) -> ClipTextEncoder:
@@ -419,7 +423,7 @@ InstantidSingleConceptPipeline = StableDiffusionXLInstantIDPipeline      # the n
 
 class _Unavailable:
     """Stand-in for a class the scripts import but this backend does not provide (imported-but-unused names such as
-    ``DPMSolverMultistepScheduler`` at inference_instantid.py:8, or third-party models outside the hot path): importing is fine,
+    ``models.T2IAdapter`` at inference_instantid.py:9, or third-party models outside the hot path): importing is fine,
     using it says what is missing."""
 
     def __init__(self, name: str):
@@ -455,8 +459,9 @@ def install(stub_missing: bool = True) -> List[str]:
         src.pipelines.instantid_pipeline     InstantidMultiConceptPipeline, revise_regionally_controlnet_forward
         src.pipelines.instantid_single_pieline   InstantidSingleConceptPipeline
         src.prompt_attention.p2p_attention   AttentionReplace
-        diffusers                            ControlNetModel, StableDiffusionXLPipeline (+ DPMSolverMultistepScheduler, models.T2IAdapter:
-                                             imported by the InstantID script and never used — placeholders), utils.load_image
+        diffusers                            ControlNetModel, StableDiffusionXLPipeline, DPMSolverMultistepScheduler, DDIMScheduler,
+                                             EulerDiscreteScheduler (+ models.T2IAdapter: imported by the InstantID script and never used — a
+                                             placeholder), utils.load_image
 
     so ``import omg_amd.compat as c; c.install()`` in front of the script (or ``python -c "import omg_amd.compat as c; c.install();
     import runpy; runpy.run_path('inference_lora.py', run_name='__main__')"``) is the whole edit.  Call it BEFORE the script's imports; it
@@ -532,7 +537,7 @@ def install(stub_missing: bool = True) -> List[str]:
     dm = module("diffusers.models", ControlNetModel=ControlNetModel, T2IAdapter=_Unavailable("diffusers.models.T2IAdapter"))
     du = module("diffusers.utils", load_image=load_image)
     d.__dict__.update(ControlNetModel=ControlNetModel, StableDiffusionXLPipeline=StableDiffusionXLPipeline,
-                      DPMSolverMultistepScheduler=_Unavailable("diffusers.DPMSolverMultistepScheduler"),
+                      DPMSolverMultistepScheduler=DPMSolverMultistepScheduler,
                       DDIMScheduler=DDIMScheduler, EulerDiscreteScheduler=EulerDiscreteScheduler, models=dm, utils=du)
     if stub_missing:
         def absent(name: str) -> bool:

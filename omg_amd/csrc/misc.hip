@@ -249,6 +249,74 @@ __global__ __launch_bounds__(256) void step_kernel(StepP p) {
   }
 }
 
+// step_kernel's fusion and model-input store as functions, for step_ms_kernel (step_kernel keeps its own copy unchanged):
+// nearest mask resize, new = edit * [union == 0] + sum_c region_c * [mask_c == 1] on the edited sample's (unc1, cnd1)
+__device__ __forceinline__ void step_fuse(const StepP& p, int i, int n, int HW, float& unc1, float& cnd1) {
+  const int c = i / HW; const int pix = i - c * HW;
+  const int y = pix / p.W, x = pix - y * p.W;
+  const int my = (int)(((long)y * p.Hm) / p.H), mx = (int)(((long)x * p.Wm) / p.W);
+  bool any = false;
+  float add_u = 0.f, add_c = 0.f;
+  for (int k = 0; k < p.n_concepts; ++k) {
+    if (p.masks[k] == nullptr) continue;
+    const bool on = p.masks[k][(long)my * p.Wm + mx] == 1.0f;
+    if (on) {
+      any = true;
+      if (p.region[k]) { add_u += p.region[k][i]; add_c += p.region[k][n + i]; }
+    }
+  }
+  unc1 = (any ? 0.f : unc1) + add_u;
+  cnd1 = (any ? 0.f : cnd1) + add_c;
+  if (p.fused_out) { p.fused_out[i] = unc1; p.fused_out[n + i] = cnd1; }
+}
+
+// model_input_next[4,C,H,W] = cat([latents']*2) * cin_next
+__device__ __forceinline__ void step_store_input(const StepP& p, int i, int n, float l0, float l1, float cin) {
+  const float a0 = __fmul_rn(l0, cin), a1 = __fmul_rn(l1, cin);
+  if (p.out_dtype == OMG_F16) {
+    f16* o = (f16*)p.mi_next;
+    o[i] = (f16)a0; o[n + i] = (f16)a1; o[2 * n + i] = (f16)a0; o[3 * n + i] = (f16)a1;
+  } else if (p.out_dtype == OMG_BF16) {
+    bf16* o = (bf16*)p.mi_next;
+    o[i] = (bf16)a0; o[n + i] = (bf16)a1; o[2 * n + i] = (bf16)a0; o[3 * n + i] = (bf16)a1;
+  } else {
+    float* o = (float*)p.mi_next;
+    o[i] = a0; o[n + i] = a1; o[2 * n + i] = a0; o[3 * n + i] = a1;
+  }
+}
+
+// The multistep (DPM-Solver++) form of step_kernel: the same fusion + CFG, then with row ms[*step_idx] = {a, b, cx, cm, cp, cin_next, -, -}
+//   m = a*x + b*eps ; x' = cx*x + cm*m + cp*m_prev ; hist = m
+// hist: fp32 [2,C,H,W], the data prediction of the previous step per sample.  An order-1 row has cp == 0 and hist is then not read
+// (a fresh buffer may hold NaN, and 0 * NaN is NaN); cp is uniform over the launch, so the branch does not diverge.
+__global__ __launch_bounds__(256) void step_ms_kernel(StepP p, const float* ms, float* hist) {
+  const int HW = p.H * p.W;
+  const int n = p.C * HW;
+  const float* row = ms + (long)(*p.step_idx) * 8;
+  const float a = row[0], b = row[1], cx = row[2], cm = row[3], cp = row[4], cin = row[5];
+  const bool use_prev = cp != 0.f;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    float unc0 = p.noise[0 * n + i], unc1 = p.noise[1 * n + i];
+    float cnd0 = p.noise[2 * n + i], cnd1 = p.noise[3 * n + i];
+    if (p.fuse) step_fuse(p, i, n, HW, unc1, cnd1);
+    // the same explicit sequence for both samples (stage 1: bit-identical samples, histories included)
+    const float e0 = __fmaf_rn(p.gs, __fsub_rn(cnd0, unc0), unc0);
+    const float e1 = __fmaf_rn(p.gs, __fsub_rn(cnd1, unc1), unc1);
+    const float x0 = p.latents[i], x1 = p.latents[n + i];
+    const float m0 = __fmaf_rn(b, e0, __fmul_rn(a, x0));
+    const float m1 = __fmaf_rn(b, e1, __fmul_rn(a, x1));
+    float l0 = __fmaf_rn(cm, m0, __fmul_rn(cx, x0));
+    float l1 = __fmaf_rn(cm, m1, __fmul_rn(cx, x1));
+    if (use_prev) {
+      l0 = __fmaf_rn(cp, hist[i], l0);
+      l1 = __fmaf_rn(cp, hist[n + i], l1);
+    }
+    hist[i] = m0; hist[n + i] = m1;
+    p.latents[i] = l0; p.latents[n + i] = l1;
+    if (p.mi_next) step_store_input(p, i, n, l0, l1, cin);
+  }
+}
+
 // bump the device step counter after every block of step_kernel has read it: separate 1-thread launch
 __global__ void step_advance_kernel(int* step_idx) { *step_idx = *step_idx + 1; }
 
@@ -444,24 +512,45 @@ extern "C" int omg_gather_step(int dtype, const void* table, const int32_t* step
   return omg_check_launch("gather_step");
 }
 
-extern "C" int omg_fuse_cfg_step(const omg_step_args* a, void* stream) {
-  OMG_REQUIRE(a != nullptr, "omg_fuse_cfg_step: null args");
-  OMG_REQUIRE(a->noise_pred && a->coef && a->step_idx && a->latents, "omg_fuse_cfg_step: null operand");
-  OMG_REQUIRE(a->n_concepts >= 0 && a->n_concepts <= OMG_MAX_CONCEPTS, "omg_fuse_cfg_step: n_concepts");
-  OMG_REQUIRE(a->C > 0 && a->H > 0 && a->W > 0, "omg_fuse_cfg_step: shape");
-  if (a->fuse) OMG_REQUIRE(a->Hm > 0 && a->Wm > 0, "omg_fuse_cfg_step: mask shape");
+// kernel parameters of both step entry points (arguments checked by the caller)
+static StepP step_params(const omg_step_args* a) {
   StepP p{};
   p.C = a->C; p.H = a->H; p.W = a->W; p.Hm = a->Hm; p.Wm = a->Wm; p.n_concepts = a->n_concepts; p.fuse = a->fuse;
   p.gs = a->guidance_scale; p.noise = a->noise_pred;
   for (int k = 0; k < OMG_MAX_CONCEPTS; ++k) { p.region[k] = k < a->n_concepts ? a->region_pred[k] : nullptr; p.masks[k] = k < a->n_concepts ? a->masks[k] : nullptr; }
   p.coef = a->coef; p.step_idx = a->step_idx; p.advance = a->advance;
   p.latents = a->latents; p.out_dtype = a->out_dtype; p.mi_next = a->model_input_next; p.fused_out = a->fused_noise_out;
+  return p;
+}
+
+extern "C" int omg_fuse_cfg_step(const omg_step_args* a, void* stream) {
+  OMG_REQUIRE(a != nullptr, "omg_fuse_cfg_step: null args");
+  OMG_REQUIRE(a->noise_pred && a->coef && a->step_idx && a->latents, "omg_fuse_cfg_step: null operand");
+  OMG_REQUIRE(a->n_concepts >= 0 && a->n_concepts <= OMG_MAX_CONCEPTS, "omg_fuse_cfg_step: n_concepts");
+  OMG_REQUIRE(a->C > 0 && a->H > 0 && a->W > 0, "omg_fuse_cfg_step: shape");
+  if (a->fuse) OMG_REQUIRE(a->Hm > 0 && a->Wm > 0, "omg_fuse_cfg_step: mask shape");
+  const StepP p = step_params(a);
   const int n = a->C * a->H * a->W;
   int blocks = (n + 255) / 256; if (blocks > 1024) blocks = 1024;
   hipStream_t s = (hipStream_t)stream;
   OMG_LAUNCH(step_kernel, dim3(blocks), dim3(256), 0, s, p);
   if (a->advance) OMG_LAUNCH(step_advance_kernel, dim3(1), dim3(1), 0, s, a->step_idx);
   return omg_check_launch("fuse_cfg_step");
+}
+
+extern "C" int omg_fuse_cfg_step_ms(const omg_step_args* a, const float* ms_coef, float* x0_hist, void* stream) {
+  OMG_REQUIRE(a != nullptr, "omg_fuse_cfg_step_ms: null args");
+  OMG_REQUIRE(a->noise_pred && a->step_idx && a->latents && ms_coef && x0_hist, "omg_fuse_cfg_step_ms: null operand");
+  OMG_REQUIRE(a->n_concepts >= 0 && a->n_concepts <= OMG_MAX_CONCEPTS, "omg_fuse_cfg_step_ms: n_concepts");
+  OMG_REQUIRE(a->C > 0 && a->H > 0 && a->W > 0, "omg_fuse_cfg_step_ms: shape");
+  if (a->fuse) OMG_REQUIRE(a->Hm > 0 && a->Wm > 0, "omg_fuse_cfg_step_ms: mask shape");
+  const StepP p = step_params(a);
+  const int n = a->C * a->H * a->W;
+  int blocks = (n + 255) / 256; if (blocks > 1024) blocks = 1024;
+  hipStream_t s = (hipStream_t)stream;
+  OMG_LAUNCH(step_ms_kernel, dim3(blocks), dim3(256), 0, s, p, ms_coef, x0_hist);
+  if (a->advance) OMG_LAUNCH(step_advance_kernel, dim3(1), dim3(1), 0, s, a->step_idx);
+  return omg_check_launch("fuse_cfg_step_ms");
 }
 
 extern "C" int omg_scale_model_input(int dtype, const float* latents, const float* coef_cin, int n_per_sample, void* out, void* stream) {

@@ -666,15 +666,13 @@ def copy2d(src: torch.Tensor, dst: torch.Tensor) -> None:
                                src.shape[1], _stream()), "omg_copy2d")
 
 
-def fuse_cfg_step(noise_pred: torch.Tensor, latents: torch.Tensor, coef: torch.Tensor, step_idx: torch.Tensor, *,
-                  guidance_scale: float, fuse: bool = False, region_preds: Sequence[Optional[torch.Tensor]] = (),
-                  masks: Sequence[Optional[torch.Tensor]] = (), model_input_next: Optional[torch.Tensor] = None,
-                  advance: bool = True, fused_noise_out: Optional[torch.Tensor] = None) -> None:
-    """Region fusion + CFG + scheduler step + next model input (see omg_fuse_cfg_step)."""
+def _step_args(noise_pred: torch.Tensor, latents: torch.Tensor, step_idx: torch.Tensor, guidance_scale: float, fuse: bool,
+               region_preds: Sequence[Optional[torch.Tensor]], masks: Sequence[Optional[torch.Tensor]],
+               model_input_next: Optional[torch.Tensor], advance: bool, fused_noise_out: Optional[torch.Tensor]) -> L.StepArgs:
+    """omg_step_args of both step entry points, without the scheduler table"""
     _dev(noise_pred)
     assert noise_pred.dtype == torch.float32 and noise_pred.is_contiguous() and noise_pred.shape[0] == 4
     assert latents.dtype == torch.float32 and latents.is_contiguous() and latents.shape[0] == 2
-    assert coef.dtype == torch.float32 and coef.is_contiguous() and coef.shape[-1] == 4
     assert step_idx.dtype == torch.int32
     _, Cc, H, W = noise_pred.shape
     a = L.StepArgs()
@@ -696,7 +694,7 @@ def fuse_cfg_step(noise_pred: torch.Tensor, latents: torch.Tensor, coef: torch.T
             hm, wm = m.shape
             a.masks[i] = m.data_ptr()
     a.Hm, a.Wm = (hm, wm) if hm else (H, W)
-    a.coef, a.step_idx, a.advance = coef.data_ptr(), step_idx.data_ptr(), int(advance)
+    a.step_idx, a.advance = step_idx.data_ptr(), int(advance)
     a.latents = latents.data_ptr()
     if model_input_next is not None:
         assert model_input_next.is_contiguous() and model_input_next.shape == (4, Cc, H, W)
@@ -705,7 +703,31 @@ def fuse_cfg_step(noise_pred: torch.Tensor, latents: torch.Tensor, coef: torch.T
     if fused_noise_out is not None:
         assert fused_noise_out.dtype == torch.float32 and fused_noise_out.is_contiguous()
         a.fused_noise_out = fused_noise_out.data_ptr()
+    return a
+
+
+def fuse_cfg_step(noise_pred: torch.Tensor, latents: torch.Tensor, coef: torch.Tensor, step_idx: torch.Tensor, *,
+                  guidance_scale: float, fuse: bool = False, region_preds: Sequence[Optional[torch.Tensor]] = (),
+                  masks: Sequence[Optional[torch.Tensor]] = (), model_input_next: Optional[torch.Tensor] = None,
+                  advance: bool = True, fused_noise_out: Optional[torch.Tensor] = None) -> None:
+    """Region fusion + CFG + scheduler step + next model input (see omg_fuse_cfg_step)."""
+    assert coef.dtype == torch.float32 and coef.is_contiguous() and coef.shape[-1] == 4
+    a = _step_args(noise_pred, latents, step_idx, guidance_scale, fuse, region_preds, masks, model_input_next, advance, fused_noise_out)
+    a.coef = coef.data_ptr()
     L.check(L.lib().omg_fuse_cfg_step(C.byref(a), _stream()), "omg_fuse_cfg_step")
+
+
+def fuse_cfg_step_ms(noise_pred: torch.Tensor, latents: torch.Tensor, ms_coef: torch.Tensor, x0_hist: torch.Tensor, step_idx: torch.Tensor, *,
+                     guidance_scale: float, fuse: bool = False, region_preds: Sequence[Optional[torch.Tensor]] = (),
+                     masks: Sequence[Optional[torch.Tensor]] = (), model_input_next: Optional[torch.Tensor] = None,
+                     advance: bool = True, fused_noise_out: Optional[torch.Tensor] = None) -> None:
+    """:func:`fuse_cfg_step` with a multistep scheduler update (see omg_fuse_cfg_step_ms): ``ms_coef`` (n, 8) fp32 from
+    ``DPMSolverMultistepScheduler.coef_table``; ``x0_hist`` fp32 (2, C, H, W) holds the previous step's data prediction of both samples
+    and receives this step's."""
+    assert ms_coef.dtype == torch.float32 and ms_coef.is_contiguous() and ms_coef.dim() == 2 and ms_coef.shape[-1] == 8
+    assert x0_hist.dtype == torch.float32 and x0_hist.is_contiguous() and x0_hist.shape == latents.shape and x0_hist.device == latents.device
+    a = _step_args(noise_pred, latents, step_idx, guidance_scale, fuse, region_preds, masks, model_input_next, advance, fused_noise_out)
+    L.check(L.lib().omg_fuse_cfg_step_ms(C.byref(a), ms_coef.data_ptr(), x0_hist.data_ptr(), _stream()), "omg_fuse_cfg_step_ms")
 
 
 def gather_step(table: torch.Tensor, step_idx: torch.Tensor, out: torch.Tensor) -> None:

@@ -32,7 +32,7 @@ from . import ops
 from .attention import Attention, RegionControlNet_AttnProcessor
 from .lora import LoraBank
 from .modules import LoraState, pointer_epoch
-from .schedulers import DDIMScheduler
+from .schedulers import DDIMScheduler, DPMSolverMultistepScheduler
 
 FUSION_START = 15   # `if i > 15 and stage == 2` (lora_pipeline.py:568) — absolute, not relative
 CONCEPT_LORA_SCALE = 0.8   # `cross_attention_kwargs={'scale': 0.8}` of every concept UNet call (lora_pipeline.py:596), whatever the caller passes
@@ -143,6 +143,7 @@ class StageCache:
     def __init__(self, max_entries: int = 64):
         self.entries: Dict[str, torch.Tensor] = {}
         self.base: Dict[str, Dict[int, Tuple[torch.Tensor, torch.Tensor]]] = {}
+        self.history: Dict[str, torch.Tensor] = {}
         self.max_entries = max_entries
         self.hits = 0
         self.misses = 0
@@ -183,6 +184,17 @@ class StageCache:
         if b is None or any(k not in b for k in range(first + 1, n_steps + 1)):
             return None
         return b
+
+    # ---- a multistep scheduler's state (DPMSolverMultistepScheduler): the step after the stored latents also reads the data prediction
+    # of the step before them, so an entry of such a call holds both; an entry without it is not resumed from
+    def put_history(self, key: str, x0_hist: torch.Tensor) -> None:
+        """the (2, C, H, W) data predictions of the step that produced the latents stored under ``key``"""
+        self.history[key] = x0_hist.detach().clone()
+        for k in [k for k in self.history if k not in self.entries]:      # put() evicted its entry
+            del self.history[k]
+
+    def get_history(self, key: str) -> Optional[torch.Tensor]:
+        return self.history.get(key) if key in self.entries else None
 
 
 # Parameters of the reference's ``__call__`` (lora_pipeline.py:212-255, instantid_pipeline.py:215-259) that change ITS output when they leave their
@@ -410,7 +422,8 @@ class LoraMultiConceptPipeline:
         positive] time ids, i.e. alternating, NOT [neg, neg, pos, pos] like the prompt embeddings.  Kept as executed.
         ``callback_on_step_end(pipe, i, t, {name: tensor})`` after every step with the tensors named in ``callback_on_step_end_tensor_inputs``
         (``latents`` (2, C, H/8, W/8) fp32, ``prompt_embeds`` (4, 77, Cx) = [neg, neg, pos, pos], ``negative_prompt_embeds`` (2, 77, Cx)), once per request;
-        a returned ``{"latents": ...}`` replaces the request's latents for the next step (:617-626).  Returned prompt embeddings are refused (the
+        a returned ``{"latents": ...}`` replaces the request's latents for the next step (:617-626; a multistep scheduler keeps its data
+        prediction of the step, as diffusers' ``model_outputs`` list does).  Returned prompt embeddings are refused (the
         cached cross-attention K / V would have to follow).  ``callback(i, t, latents)`` every ``callback_steps`` steps (:629-632).  Callbacks switch off
         ``dedup`` / ``stage_cache`` (they may make the two samples differ) and run between hipGraph replays.
         ``identitynet`` (InstantID, instantid_pipeline.py:638-674): ControlNet on the CONCEPT pass fed with the face tokens and
@@ -612,6 +625,7 @@ class LoraMultiConceptPipeline:
         # ---- stage cache: everything that determines the latents entering step fusion_start + 1 of request j; decided in
         # front of the engine because a resumed call without `unc0` runs a different row plan
         first = 0
+        multistep = isinstance(self.scheduler, DPMSolverMultistepScheduler)    # omg_fuse_cfg_step_ms + the history buffer eng.x0_hist
         cache_keys: List[str] = []
         cache_hit = None
         base_traj = None                      # drop_unc0: per step k the (n, C, H, W) latents / model inputs of the base samples
@@ -634,6 +648,9 @@ class LoraMultiConceptPipeline:
                 cn_img = None if not use_cn else (controlnet_image if controlnet_image.shape[0] == 1 else controlnet_image[j: j + 1])
                 cache_keys.append(StageCache.digest(common, coef_key, lats[j], ehs_l[j], text_l[j], cn_img))
             hit = [stage_cache.get(k) for k in cache_keys]
+            if multistep:      # the first resumed step also reads the data prediction of the step in front of it
+                hist_hit = [stage_cache.get_history(k) for k in cache_keys]
+                hit = [h if m is not None else None for h, m in zip(hit, hist_hit)]
             if fuse_possible and all(h is not None for h in hit):
                 first, cache_hit = fusion_start + 1, hit                 # every request resumes: the plain steps are not run at all
                 stage_cache.hits += n
@@ -666,6 +683,8 @@ class LoraMultiConceptPipeline:
             # drop0: the rows of `unc0` are never written — zeros, so that the step kernel's (discarded) update of the base sample stays finite
             eng.nout = (torch.zeros if drop0 else torch.empty)((nb, Cl, Hl, Wl), dtype=torch.float32, device=dev)
             eng.step_idx = torch.zeros(1, dtype=torch.int32, device=dev)
+            if multistep:      # the previous step's data prediction of every sample (captured graphs point at it); order-1 steps do not read it
+                eng.x0_hist = torch.zeros((2 * n, Cl, Hl, Wl), dtype=torch.float32, device=dev)
             eng.ehs = torch.empty_like(ehs)
             eng.emb_main = torch.empty((S, nm, D), dtype=dt, device=dev)
             eng.emb_cur_main = torch.empty((nm, D), dtype=dt, device=dev)
@@ -760,6 +779,8 @@ class LoraMultiConceptPipeline:
         xin, nout, step_idx, coef = eng.xin, eng.nout, eng.step_idx, eng.coef
         if cache_hit is not None:                                        # resume (decided in front of the engine, above)
             lat.copy_(torch.cat([h.to(dev) for h in cache_hit], dim=0))
+            if multistep:
+                eng.x0_hist.copy_(torch.cat([h.to(dev) for h in hist_hit], dim=0))
             step_idx.fill_(first)
             if controller is not None:
                 controller.cur_step = first                              # the host-side counters the skipped steps would have ticked
@@ -916,9 +937,7 @@ class LoraMultiConceptPipeline:
                 self.unet.set_lora_state(None)
             nout[:nm].view(n, 2, 2, Cl, Hl, Wl).copy_(y2.view(n, 2, 1, Cl, Hl, Wl).expand(n, 2, 2, Cl, Hl, Wl))
             for j in range(n):
-                ops.fuse_cfg_step(nout[4 * j: 4 * j + 4], lat[2 * j: 2 * j + 2], coef, step_idx, guidance_scale=guidance_scale,
-                                  fuse=False, region_preds=[None] * K, masks=[None] * K,
-                                  model_input_next=xin[4 * j: 4 * j + 4], advance=(j == n - 1))
+                scheduler_step(j, fuse=False, region_preds=[None] * K, masks=[None] * K, advance=(j == n - 1))
 
         def step_body(fused: bool, twin_step: bool = False):
             """One denoising iteration; every per-step quantity is selected by the DEVICE step counter."""
@@ -973,9 +992,17 @@ class LoraMultiConceptPipeline:
                     for jj, c in enumerate(active):
                         r0 = region_rows(j) + 2 * jj
                         regs[c] = nout[r0: r0 + 2]
+                scheduler_step(j, fuse=fused, region_preds=regs, masks=eng.masks[j] if fused else [None] * K, advance=(j == n - 1))
+
+        def scheduler_step(j: int, **kw):
+            """request j's fusion + CFG + scheduler update + next model input: the one-step linear table (DDIM, Euler) or the
+            multistep one with the request's rows of the history buffer (DPM-Solver++)"""
+            if multistep:
+                ops.fuse_cfg_step_ms(nout[4 * j: 4 * j + 4], lat[2 * j: 2 * j + 2], coef, eng.x0_hist[2 * j: 2 * j + 2], step_idx,
+                                     guidance_scale=guidance_scale, model_input_next=xin[4 * j: 4 * j + 4], **kw)
+            else:
                 ops.fuse_cfg_step(nout[4 * j: 4 * j + 4], lat[2 * j: 2 * j + 2], coef, step_idx, guidance_scale=guidance_scale,
-                                  fuse=fused, region_preds=regs, masks=eng.masks[j] if fused else [None] * K,
-                                  model_input_next=xin[4 * j: 4 * j + 4], advance=(j == n - 1))
+                                  model_input_next=xin[4 * j: 4 * j + 4], **kw)
 
         def shard_forward(fused: bool, _tw: bool = False):
             """This rank's units of the step: main blocks first, then concept pairs, as one compact batch."""
@@ -1072,6 +1099,8 @@ class LoraMultiConceptPipeline:
             if cache_keys and first == 0 and i == fusion_start:         # the latents entering the first fused step of a stage-2 call
                 for j, k in enumerate(cache_keys):
                     stage_cache.put(k, lat[2 * j: 2 * j + 2])
+                    if multistep:                                       # ... and the data prediction that step reads besides them
+                        stage_cache.put_history(k, eng.x0_hist[2 * j: 2 * j + 2])
             if cache_keys and first == 0 and i >= fusion_start:         # ... and the base sample's way from there on (drop_unc0)
                 for j, k in enumerate(cache_keys):
                     stage_cache.put_base(k, i + 1, lat[2 * j: 2 * j + 1], xin[4 * j + 2: 4 * j + 3])
