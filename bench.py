@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — images/sec of OMG's stage-2 denoising call on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One "step" = one batch of `--images-per-step` (default 8) independent requests, each a complete stage-2 call of the
@@ -16,11 +16,13 @@ rank-64 LoRAs on every attention/FF Linear, overlapping region masks, fusion for
 Inputs are resident in HBM before the timed region.  N > 1: one process per GPU, each rank runs K steps
 (weak scaling), final latents all-gathered over RCCL per step; value = N * K * images_per_step / max-over-ranks time.
 
-Prints ONE JSON line (rank 0).  Extra objects: "roofline" (GEMM/conv kernel family, MFMA-bound, HIP-event
-timed in an instrumented pass of one plain + one fused denoising step) and "cpu_baseline" (the fp32 oracle on
-the host cores, bounded sample, extrapolated).  "value" is the reference's as-executed work (336 sample-forwards per
-image); "value_dedup" is the same images with the exactly redundant sample-forwards of steps 0..15 executed once
-(bitwise the same latents, tests/test_pipeline_gpu.py), timed in a second, shorter region.
+Prints ONE JSON line (rank 0).  "value" is the reference's as-executed work (336 sample-forwards per image).  A plain run does
+only what that figure needs: set up, W warm-up steps, the K timed steps, --dump-outputs, the line.  `--full` adds everything
+else: "power" (socket power / shader clock polled during the timed region) and, after that region, "value_dedup" (the
+same images with the exactly redundant sample-forwards of steps 0..15 executed once; bitwise the same latents,
+tests/test_pipeline_gpu.py; timed in a second, shorter region), "roofline" (GEMM/conv kernel family, MFMA-bound, HIP-event
+timed in an instrumented pass of one plain + one fused denoising step; --by-shape) and "cpu_baseline" (the fp32 oracle on the
+host cores, bounded sample, extrapolated).  The --no-* switches and --dedup-steps / --by-shape select among these.
 
 `--dump-outputs DIR` writes what the last timed step computed (rank 0's requests) as DIR/<name>.npy in float32: `latents` (requests, 2 samples,
 4, h, w) and `images` (decoded images, requests x 2 samples x 3 x H x W; absent with --no-vae).  An output of more than 2^21 values is
@@ -146,19 +148,21 @@ def main():
                          "everything else fp16 as in the default mode; NOT the headline configuration")
     ap.add_argument("--scheduler", default="ddim", choices=["ddim", "euler"])
     ap.add_argument("--denoise-steps", type=int, default=50)
+    ap.add_argument("--full", action="store_true", help="also measure power / clock (during the timed region), value_dedup, the roofline and the CPU "
+                    "baseline (after it), each unless its --no-* switch is given; without it the run measures the headline figure only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--cpu-latent", type=int, default=128, choices=[64, 128])
-    ap.add_argument("--dedup-steps", type=int, default=-1, help="steps of the second timed region (value_dedup); -1 = min(--steps, 2), 0 = skip")
+    ap.add_argument("--dedup-steps", type=int, default=-1, help="with --full: steps of the second timed region (value_dedup); -1 = min(--steps, 2), 0 = skip")
     ap.add_argument("--tiny", action="store_true", help="debug: tiny UNet (NOT a valid benchmark)")
     ap.add_argument("--images-per-step", type=int, default=8, help="independent requests run in lock-step per step (one batched UNet forward)")
-    ap.add_argument("--by-shape", default="", help="also write the roofline leg's per-shape table (ms per bench step, TF/s) to this file")
+    ap.add_argument("--by-shape", default="", help="with --full: also write the roofline leg's per-shape table (ms per bench step, TF/s) to this file")
     ap.add_argument("--no-vae", action="store_true", help="stop at the latents (skip the VAE decode that ends the reference's stage-2 call)")
     ap.add_argument("--vae-16bit", action="store_true", help="decode in bf16 storage instead of the reference's fp32 up blocks (faster, NOT the reference's precision)")
     ap.add_argument("--fp8-linear-only", action="store_true", help="with --dtype fp8: keep every convolution in fp16 (round-2 first fp8 line)")
     ap.add_argument("--fp8-classes", default="all", help="with --dtype fp8: which layer classes run on the MX-fp8 MFMA — a preset of omg_amd.unet.MX8_PRESETS "
                     "(all | safe | none) or a comma list of omg_amd.unet.MX8_CLASSES (profiles/r04_mx8_sensitivity.json is the per-class error table)")
-    ap.add_argument("--no-power", action="store_true", help="do not poll rocm-smi for power / clock during the timed region")
+    ap.add_argument("--no-power", action="store_true", help="with --full: do not poll rocm-smi for power / clock during the timed region")
     ap.add_argument("--no-graph", action="store_true", help="run the step loop eagerly instead of replaying captured hipGraphs")
     ap.add_argument("--shard", default="images", choices=["images", "concept"],
                     help="N > 1 only.  images (default, throughput, weak scaling): every rank runs its own requests, one all_gather of the final latents. "
@@ -172,6 +176,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full and (args.by_shape or args.dedup_steps > 0):
+        ap.error("--by-shape and --dedup-steps measure beyond the headline figure: add --full")
     if args.config3:
         args.images_per_step = 4
 
@@ -259,7 +265,7 @@ def main():
     for i in range(args.warmup):
         lat = run_step(inputs[i])
         gather(lat)
-    sampler = PowerSampler(local) if rank == 0 and not args.no_power else None
+    sampler = PowerSampler(local) if rank == 0 and args.full and not args.no_power else None
     parallel.barrier()
     torch.cuda.synchronize()
     if sampler is not None:
@@ -284,8 +290,8 @@ def main():
 
     # second timed region: the same requests with the exactly redundant forwards executed once (same barrier / sync bracket)
     n_dd = min(args.steps, 2) if args.dedup_steps < 0 else min(args.dedup_steps, n_steps)
-    if by_concept:
-        n_dd = 0                                              # the twin regime and the unit split are alternatives
+    if by_concept or not args.full:
+        n_dd = 0                                              # concept: the twin regime and the unit split are alternatives
     dedup = None
     if n_dd > 0:
         lat_full = lat
@@ -341,7 +347,7 @@ def main():
 
     if sampler is not None:
         out["power"] = sampler.summary()
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # instrumented eager passes: HIP events around every GEMM/conv/attention launch of 2 plain and of 2 fused denoising
         # steps, combined with the weights of the timed workload (fusion fires for steps i > 15: 16 plain + 34 fused of 50)
         def instrumented(fusion_start):
@@ -428,7 +434,7 @@ def main():
                 f.write(f"# per bench step ({ips} images): kind, shape tag, launches, ms, share, TF/s; total {tot:.1f} ms\n")
                 for key, ms, fl, n in rows:
                     f.write(f"{key[0]:5s} {str(key[1]):56s} n={n:7.0f} ms={ms:9.2f} ({100 * ms / tot:4.1f}%) {fl / ms / 1e9 if ms else 0:7.1f} TF/s\n")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:      # the host-core baseline is reported at N = 1 only
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:      # the host-core baseline is reported at N = 1 only
         out["cpu_baseline"] = cpu_baseline(args)
         # BASELINE configs[0] — the reference's own CPU-runnable case (512^2, 10 DDIM steps, 1 concept, no LoRA) — timed FOR REAL at full width, no
         # extrapolation: the oracle's 10-step stage-2 call on the GPU box's host cores (tests/test_config0_fullwidth_gpu.py, ~4 minutes per stage: too long

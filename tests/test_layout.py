@@ -129,6 +129,13 @@ def test_bench_rejects_fewer_than_one_timed_step():
     assert r.returncode == 2 and "--steps" in r.stderr, r.stderr
 
 
+@pytest.mark.parametrize("extra", [["--by-shape", "shapes.txt"], ["--dedup-steps", "2"]])
+def test_bench_extras_without_full_are_refused(extra):
+    """A plain run measures the headline only: asking it for a roofline table or a dedup region without --full is an error, not a no-op."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--full" in r.stderr, r.stderr
+
+
 def test_groupnorm_workspace_holds_partials_and_folded_statistics():
     from omg_amd import _lib
     lib = _lib.lib()

@@ -18,5 +18,5 @@ timeout 300 python tools/attn_bench.py 2>&1 | grep -v libdrm | tee $O/attn_bench
 timeout 400 python tools/vs_hipblaslt.py --rounds 3 2>&1 | grep -v libdrm | tee $O/vs_hipblaslt.log | tail -11
 timeout 400 python tools/gemm_cold.py --rounds 3 2>&1 | grep -v libdrm | tee $O/gemm_hot_cold.log | tail -7
 timeout 300 python tools/pack_time.py 2>&1 | grep -v libdrm | tee $O/pack_time.log | tail -5
-python bench.py --gpus 1 --steps 2 --warmup 1 --dtype fp8 --no-cpu-baseline --by-shape $O/by_shape_fp8_v1.txt > $O/bench_fp8_v1.json 2> $O/bench_fp8_v1.err
+python bench.py --full --gpus 1 --steps 2 --warmup 1 --dtype fp8 --no-cpu-baseline --by-shape $O/by_shape_fp8_v1.txt > $O/bench_fp8_v1.json 2> $O/bench_fp8_v1.err
 head -c 300 $O/bench_fp8_v1.json; echo

@@ -6,7 +6,7 @@ O=gpurun_out/r05
 mkdir -p $O
 timeout 1500 python -m pytest tests -m gpu -x -q --durations=10 > $O/fourth_pytest_gpu.log 2>&1
 tail -16 $O/fourth_pytest_gpu.log
-B="--steps 2 --warmup 1 --dedup-steps 0 --no-cpu-baseline"
+B="--full --steps 2 --warmup 1 --dedup-steps 0 --no-cpu-baseline"
 timeout 600 python bench.py $B --by-shape $O/fourth_by_shape.txt > $O/fourth_bench.json 2> $O/fourth_bench.err; head -c 300 $O/fourth_bench.json; echo
 OMG_ATTN_VARIANT=0x10000 timeout 600 python bench.py $B --by-shape $O/fourth_by_shape_natural.txt > $O/fourth_bench_natural.json 2> $O/fourth_bench_natural.err; head -c 300 $O/fourth_bench_natural.json; echo
 timeout 300 python tools/ksched_ab.py 25,16409,32793 3 k 2>&1 | grep -v libdrm | tee $O/fourth_walk_group_ab.log

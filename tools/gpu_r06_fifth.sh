@@ -7,7 +7,7 @@ mkdir -p $O
 timeout 900 python -m pytest tests/test_mx8_gpu.py -x -q --durations=5 > $O/fifth_mx8_tests.log 2>&1
 tail -12 $O/fifth_mx8_tests.log
 timeout 600 python tools/mx8_bench.py 2>&1 | grep -v libdrm | tee $O/mx8_bench.log | tail -12
-B="--steps 2 --warmup 1 --dtype fp8 --no-cpu-baseline --dedup-steps 0"
+B="--full --steps 2 --warmup 1 --dtype fp8 --no-cpu-baseline --dedup-steps 0"
 OMG_MX8_SPLIT=0x800c python bench.py $B --by-shape $O/by_shape_fp8_one_tile.txt > $O/bench_fp8_one_tile.json 2> $O/bench_fp8_one_tile.err
 python bench.py $B --by-shape $O/by_shape_fp8_persistent.txt > $O/bench_fp8_persistent.json 2> $O/bench_fp8_persistent.err
 OMG_MX8_SPLIT=0x800c python bench.py $B --no-roofline > $O/bench_fp8_one_tile_b.json 2> $O/bench_fp8_one_tile_b.err

@@ -8,7 +8,7 @@ python -m pytest tests/test_kernels_gpu.py tests/test_benchsize_parity_gpu.py -x
 tail -5 $O/sixth_tests.log
 timeout 500 python tools/ksched_ab.py 33554457,25 5 n320 2>&1 | grep -v libdrm | tee $O/res_form6_ab_n320.log
 timeout 400 python tools/ksched_ab.py 33554457,25 5 slots 2>&1 | grep -v libdrm | tee $O/res_form6_ab_slots.log
-B="--steps 2 --warmup 1 --no-cpu-baseline --dedup-steps 0"
+B="--full --steps 2 --warmup 1 --no-cpu-baseline --dedup-steps 0"
 OMG_GEMM_VARIANT=33554432 python bench.py $B --by-shape $O/by_shape_fp16_form2.txt > $O/bench_fp16_form2.json 2> $O/bench_fp16_form2.err
 python bench.py $B --by-shape $O/by_shape_fp16_form6.txt > $O/bench_fp16_form6.json 2> $O/bench_fp16_form6.err
 OMG_GEMM_VARIANT=33554432 python bench.py $B --no-roofline > $O/bench_fp16_form2b.json 2> $O/bench_fp16_form2b.err

@@ -11,8 +11,8 @@ for r in 1 2; do
   echo "== DMA-first prologue (this build), DEN 1"; timeout 300 python tools/attn_bench.py 0 2>&1 | grep "^(" | head -2
 done 2>&1 | tee $O/attn_prologue_ab.log
 timeout 300 python tools/mfma_shape_probe.py 3 2>&1 | grep -v libdrm | tee $O/mfma_shape_probe.log
-OMG_ATTN_VARIANT=7 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --dedup-steps 0 --by-shape $O/by_shape_fp16_den0.txt > $O/bench_fp16_den0.json 2> $O/bench_fp16_den0.err
-python bench.py --steps 2 --warmup 1 --no-cpu-baseline --dedup-steps 0 --by-shape $O/by_shape_fp16_den1.txt > $O/bench_fp16_den1.json 2> $O/bench_fp16_den1.err
+OMG_ATTN_VARIANT=7 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --dedup-steps 0 --by-shape $O/by_shape_fp16_den0.txt > $O/bench_fp16_den0.json 2> $O/bench_fp16_den0.err
+python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --dedup-steps 0 --by-shape $O/by_shape_fp16_den1.txt > $O/bench_fp16_den1.json 2> $O/bench_fp16_den1.err
 OMG_ATTN_VARIANT=7 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --dedup-steps 0 --no-roofline > $O/bench_fp16_den0b.json 2> $O/bench_fp16_den0b.err
 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --dedup-steps 0 --no-roofline > $O/bench_fp16_den1b.json 2> $O/bench_fp16_den1b.err
 for f in den0 den1 den0b den1b; do python -c "import json;d=json.load(open('$O/bench_fp16_$f.json'));print('$f', d['value'], d.get('roofline',{}).get('attn_kernel'))"; done
