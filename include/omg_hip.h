@@ -360,6 +360,13 @@ int omg_fuse_cfg_step(const omg_step_args* a, void* stream);
  *           (order 1: the first step) do not read it, so it needs no initialisation. */
 int omg_fuse_cfg_step_ms(const omg_step_args* a, const float* ms_coef, float* x0_hist, void* stream);
 
+/* omg_fuse_cfg_step_noise — omg_fuse_cfg_step for a STOCHASTIC scheduler (Euler-ancestral, DDIM with eta > 0,
+ * omg_amd/schedulers.py).  Reads the same table a->coef [n_steps][4], now with column 3 in use:
+ *             row = {cx, ce, cin_next, cz}; latents' = cx*latents + ce*eps + cz*z ; model_input' = cin_next * latents'
+ * z : fp32 Gaussian noise of this request, [2,C,H,W] per step; step s (= *a->step_idx, read on the device) is at
+ *     z + s * z_step_stride (elements, >= 2*C*H*W).  Rows with cz == 0 do not read it. */
+int omg_fuse_cfg_step_noise(const omg_step_args* a, const float* z, int64_t z_step_stride, void* stream);
+
 /* out[0:n] = table[*step_idx * n : (*step_idx + 1) * n]: per-step conditioning (time/text embedding rows, hoisted out
  * of the loop by the host) selected with the DEVICE step counter, so a captured step graph has no host argument. */
 int omg_gather_step(int dtype, const void* table, const int32_t* step_idx, void* out, int64_t n_per_step, void* stream);

@@ -127,6 +127,7 @@ SYMBOLS = {
     "omg_copy2d": (c_i32, [c_i32, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp]),
     "omg_fuse_cfg_step": (c_i32, [C.POINTER(StepArgs), c_vp]),
     "omg_fuse_cfg_step_ms": (c_i32, [C.POINTER(StepArgs), c_vp, c_vp, c_vp]),
+    "omg_fuse_cfg_step_noise": (c_i32, [C.POINTER(StepArgs), c_vp, c_i64, c_vp]),
     "omg_scale_model_input": (c_i32, [c_i32, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "omg_gather_step": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "omg_attn_probs": (c_i32, [C.POINTER(AttnArgs), c_vp, c_vp]),

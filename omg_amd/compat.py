@@ -41,7 +41,7 @@ from .lora import LoraBank
 from .pipeline import (ConceptModels, InstantidMultiConceptPipeline as _InstantidPipe, LoraMultiConceptPipeline as _LoraPipe,
                        StableDiffusionXLPipelineOutput)
 from .resampler import Resampler
-from .schedulers import DDIMScheduler, DPMSolverMultistepScheduler, EulerDiscreteScheduler
+from .schedulers import DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler, EulerDiscreteScheduler
 from .text_encoder import ClipTextConfig, ClipTextEncoder, make_encode_prompt
 from .unet import UNet2DConditionModel, UNetConfig
 from .vae import AutoencoderKLDecoder, VaeConfig
@@ -121,6 +121,8 @@ class _Components:
         self.scheduler_class = DDIMScheduler if "DDIM" in name else EulerDiscreteScheduler     # SDXL-base ships EulerDiscrete
         if name == "DPMSolverMultistepScheduler":       # built from the file's keys (an unsupported option raises here)
             self.scheduler_class = functools.partial(DPMSolverMultistepScheduler.from_config, sched_cfg)
+        if name == "EulerAncestralDiscreteScheduler":   # likewise: not the deterministic Euler-discrete, which would give another image
+            self.scheduler_class = functools.partial(EulerAncestralDiscreteScheduler.from_config, sched_cfg)
         self.bank = LoraBank(self.unet, [])
 
     def _text_encoder(self, sub: str, with_projection: bool) -> ClipTextEncoder:
@@ -460,8 +462,8 @@ def install(stub_missing: bool = True) -> List[str]:
         src.pipelines.instantid_single_pieline   InstantidSingleConceptPipeline
         src.prompt_attention.p2p_attention   AttentionReplace
         diffusers                            ControlNetModel, StableDiffusionXLPipeline, DPMSolverMultistepScheduler, DDIMScheduler,
-                                             EulerDiscreteScheduler (+ models.T2IAdapter: imported by the InstantID script and never used — a
-                                             placeholder), utils.load_image
+                                             EulerDiscreteScheduler, EulerAncestralDiscreteScheduler (+ models.T2IAdapter: imported by
+                                             the InstantID script and never used — a placeholder), utils.load_image
 
     so ``import omg_amd.compat as c; c.install()`` in front of the script (or ``python -c "import omg_amd.compat as c; c.install();
     import runpy; runpy.run_path('inference_lora.py', run_name='__main__')"``) is the whole edit.  Call it BEFORE the script's imports; it
@@ -538,7 +540,8 @@ def install(stub_missing: bool = True) -> List[str]:
     du = module("diffusers.utils", load_image=load_image)
     d.__dict__.update(ControlNetModel=ControlNetModel, StableDiffusionXLPipeline=StableDiffusionXLPipeline,
                       DPMSolverMultistepScheduler=DPMSolverMultistepScheduler,
-                      DDIMScheduler=DDIMScheduler, EulerDiscreteScheduler=EulerDiscreteScheduler, models=dm, utils=du)
+                      DDIMScheduler=DDIMScheduler, EulerDiscreteScheduler=EulerDiscreteScheduler,
+                      EulerAncestralDiscreteScheduler=EulerAncestralDiscreteScheduler, models=dm, utils=du)
     if stub_missing:
         def absent(name: str) -> bool:
             if name in sys.modules:

@@ -317,6 +317,34 @@ __global__ __launch_bounds__(256) void step_ms_kernel(StepP p, const float* ms, 
   }
 }
 
+// The stochastic form of step_kernel (Euler-ancestral, DDIM with eta > 0): the same fusion + CFG and one-step map from the same
+// (n, 4) table, then row[3] = cz times this step's Gaussian noise z + step * zs, fp32 [2,C,H,W] drawn by the host from the request's generator
+//   x' = cx*x + ce*eps ; x' = x' + cz*z
+// A row with cz == 0 (the last ancestral step) does not read z; cz is uniform over the launch, so the branch does not diverge.
+__global__ __launch_bounds__(256) void step_noise_kernel(StepP p, const float* z, long zs) {
+  const int HW = p.H * p.W;
+  const int n = p.C * HW;
+  const int step = *p.step_idx;
+  const float cx = p.coef[step * 4 + 0], ce = p.coef[step * 4 + 1], cin = p.coef[step * 4 + 2], cz = p.coef[step * 4 + 3];
+  const float* zt = z + (long)step * zs;
+  const bool use_z = cz != 0.f;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    float unc0 = p.noise[0 * n + i], unc1 = p.noise[1 * n + i];
+    float cnd0 = p.noise[2 * n + i], cnd1 = p.noise[3 * n + i];
+    if (p.fuse) step_fuse(p, i, n, HW, unc1, cnd1);
+    const float e0 = __fmaf_rn(p.gs, __fsub_rn(cnd0, unc0), unc0);
+    const float e1 = __fmaf_rn(p.gs, __fsub_rn(cnd1, unc1), unc1);
+    float l0 = __fmaf_rn(ce, e0, __fmul_rn(cx, p.latents[i]));
+    float l1 = __fmaf_rn(ce, e1, __fmul_rn(cx, p.latents[n + i]));
+    if (use_z) {
+      l0 = __fmaf_rn(cz, zt[i], l0);
+      l1 = __fmaf_rn(cz, zt[n + i], l1);
+    }
+    p.latents[i] = l0; p.latents[n + i] = l1;
+    if (p.mi_next) step_store_input(p, i, n, l0, l1, cin);
+  }
+}
+
 // bump the device step counter after every block of step_kernel has read it: separate 1-thread launch
 __global__ void step_advance_kernel(int* step_idx) { *step_idx = *step_idx + 1; }
 
@@ -551,6 +579,22 @@ extern "C" int omg_fuse_cfg_step_ms(const omg_step_args* a, const float* ms_coef
   OMG_LAUNCH(step_ms_kernel, dim3(blocks), dim3(256), 0, s, p, ms_coef, x0_hist);
   if (a->advance) OMG_LAUNCH(step_advance_kernel, dim3(1), dim3(1), 0, s, a->step_idx);
   return omg_check_launch("fuse_cfg_step_ms");
+}
+
+extern "C" int omg_fuse_cfg_step_noise(const omg_step_args* a, const float* z, int64_t z_step_stride, void* stream) {
+  OMG_REQUIRE(a != nullptr, "omg_fuse_cfg_step_noise: null args");
+  OMG_REQUIRE(a->noise_pred && a->coef && a->step_idx && a->latents && z, "omg_fuse_cfg_step_noise: null operand");
+  OMG_REQUIRE(a->n_concepts >= 0 && a->n_concepts <= OMG_MAX_CONCEPTS, "omg_fuse_cfg_step_noise: n_concepts");
+  OMG_REQUIRE(a->C > 0 && a->H > 0 && a->W > 0, "omg_fuse_cfg_step_noise: shape");
+  OMG_REQUIRE(z_step_stride >= 2L * a->C * a->H * a->W, "omg_fuse_cfg_step_noise: z_step_stride");
+  if (a->fuse) OMG_REQUIRE(a->Hm > 0 && a->Wm > 0, "omg_fuse_cfg_step_noise: mask shape");
+  const StepP p = step_params(a);
+  const int n = a->C * a->H * a->W;
+  int blocks = (n + 255) / 256; if (blocks > 1024) blocks = 1024;
+  hipStream_t s = (hipStream_t)stream;
+  OMG_LAUNCH(step_noise_kernel, dim3(blocks), dim3(256), 0, s, p, z, (long)z_step_stride);
+  if (a->advance) OMG_LAUNCH(step_advance_kernel, dim3(1), dim3(1), 0, s, a->step_idx);
+  return omg_check_launch("fuse_cfg_step_noise");
 }
 
 extern "C" int omg_scale_model_input(int dtype, const float* latents, const float* coef_cin, int n_per_sample, void* out, void* stream) {

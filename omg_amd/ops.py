@@ -730,6 +730,21 @@ def fuse_cfg_step_ms(noise_pred: torch.Tensor, latents: torch.Tensor, ms_coef: t
     L.check(L.lib().omg_fuse_cfg_step_ms(C.byref(a), ms_coef.data_ptr(), x0_hist.data_ptr(), _stream()), "omg_fuse_cfg_step_ms")
 
 
+def fuse_cfg_step_noise(noise_pred: torch.Tensor, latents: torch.Tensor, coef: torch.Tensor, z: torch.Tensor, step_idx: torch.Tensor, *,
+                        guidance_scale: float, fuse: bool = False, region_preds: Sequence[Optional[torch.Tensor]] = (),
+                        masks: Sequence[Optional[torch.Tensor]] = (), model_input_next: Optional[torch.Tensor] = None,
+                        advance: bool = True, fused_noise_out: Optional[torch.Tensor] = None) -> None:
+    """:func:`fuse_cfg_step` with a stochastic scheduler update (see omg_fuse_cfg_step_noise): ``coef`` (n, 4) fp32 whose column 3 is
+    the noise coefficient; ``z`` fp32 (n, 2, C, H, W), one noise draw per step (the step dimension may be strided, each step's block
+    contiguous), selected on the device by ``step_idx``."""
+    assert coef.dtype == torch.float32 and coef.is_contiguous() and coef.dim() == 2 and coef.shape[-1] == 4
+    assert z.dtype == torch.float32 and z.dim() == 5 and z.shape[0] == coef.shape[0] and z.shape[1:] == latents.shape and z.device == latents.device
+    assert z[0].is_contiguous() and z.stride(0) >= z[0].numel()
+    a = _step_args(noise_pred, latents, step_idx, guidance_scale, fuse, region_preds, masks, model_input_next, advance, fused_noise_out)
+    a.coef = coef.data_ptr()
+    L.check(L.lib().omg_fuse_cfg_step_noise(C.byref(a), z.data_ptr(), z.stride(0), _stream()), "omg_fuse_cfg_step_noise")
+
+
 def gather_step(table: torch.Tensor, step_idx: torch.Tensor, out: torch.Tensor) -> None:
     """out = table[step_idx] with the step index read ON THE DEVICE (table: (S, ...), out: (...))."""
     _dev(table)

@@ -32,7 +32,7 @@ from . import ops
 from .attention import Attention, RegionControlNet_AttnProcessor
 from .lora import LoraBank
 from .modules import LoraState, pointer_epoch
-from .schedulers import DDIMScheduler, DPMSolverMultistepScheduler
+from .schedulers import DDIMScheduler, DPMSolverMultistepScheduler, draw_noise, is_stochastic
 
 FUSION_START = 15   # `if i > 15 and stage == 2` (lora_pipeline.py:568) — absolute, not relative
 CONCEPT_LORA_SCALE = 0.8   # `cross_attention_kwargs={'scale': 0.8}` of every concept UNet call (lora_pipeline.py:596), whatever the caller passes
@@ -316,8 +316,6 @@ class LoraMultiConceptPipeline:
             raise L.OmgHipError(f"{n_nets} ControlNets need a list of {n_nets} conditioning images (lora_pipeline.py:366-383)")
         if image is not None and controlnet is None:
             raise L.OmgHipError("image= needs a ControlNet: pass controlnet=omg_amd.controlnet.ControlNetModel(...)")
-        if eta != 0.0:
-            raise L.OmgHipError("eta != 0 (stochastic DDIM) is not used by OMG and is not supported")
         lora_list = list(lora_list or [])
         # ---- 3. prompt embeddings (global on the main pipe; per-region on the concept pipe)
         if prompt_embeds is None:
@@ -359,7 +357,7 @@ class LoraMultiConceptPipeline:
                                  controlnet_conditioning_scale=cn_scale, dedup=dedup, stage_cache=stage_cache, drop_unc0=drop_unc0,
                                  guess_mode=guess_mode and image is not None, control_guidance_start=cg_start, control_guidance_end=cg_end,
                                  negative_original_size=neg_cond[0], negative_crops_coords_top_left=neg_cond[1], negative_target_size=neg_cond[2],
-                                 **callbacks)[0]
+                                 eta=eta, **callbacks)[0]
         if trajectory is not None:
             trajectory.extend(t[0] for t in traj_many)
         images = self._postprocess(lat, output_type)
@@ -402,7 +400,8 @@ class LoraMultiConceptPipeline:
                       stage_cache: Optional[StageCache] = None, drop_unc0: bool = False, guess_mode: bool = False,
                       control_guidance_start=0.0, control_guidance_end=1.0, negative_original_size=None, negative_crops_coords_top_left=(0, 0),
                       negative_target_size=None, callback: Optional[Callable] = None, callback_steps: Optional[int] = None,
-                      callback_on_step_end: Optional[Callable] = None, callback_on_step_end_tensor_inputs=("latents",)) -> torch.Tensor:
+                      callback_on_step_end: Optional[Callable] = None, callback_on_step_end_tensor_inputs=("latents",),
+                      eta: float = 0.0) -> torch.Tensor:
         """Each request: dict(prompt_embeds (2,77,Cx), negative_prompt_embeds, pooled_prompt_embeds (2,P),
         negative_pooled_prompt_embeds, region_prompt_embeds [(neg, pos, neg_pooled, pos_pooled)] * K, region_masks [K],
         latents | generator).  Returns final latents (n, 2, C, H/8, W/8): [base sample, edited sample] per request.
@@ -454,7 +453,18 @@ class LoraMultiConceptPipeline:
         ``concept_shard`` (:class:`omg_amd.parallel.ConceptShard`, every rank of its group calls with the SAME requests): the step's
         independent forward units — the main block of a request, each concept pair — are split over the ranks, one all_gather
         per step exchanges the noise predictions and every rank applies the same fusion + CFG + scheduler kernel, so all ranks
-        return the same latents, bitwise equal to the unsharded call (SURVEY §8(e) finer-grain option; latency, not throughput)."""
+        return the same latents, bitwise equal to the unsharded call (SURVEY §8(e) finer-grain option; latency, not throughput).
+
+        Stochastic steps: with :class:`omg_amd.schedulers.EulerAncestralDiscreteScheduler`, or :class:`DDIMScheduler` and ``eta > 0``, every step adds
+        fresh Gaussian noise (the reference passes ``eta`` and ``generator`` to ``scheduler.step``, lora_pipeline.py:615; other schedulers ignore
+        ``eta``, as diffusers' ``prepare_extra_step_kwargs`` does).  Right after a request's initial latents its ``generator`` draws S tensors
+        (2, C, H/8, W/8), one per step, in step order: ``torch.randn(..., generator=g, device=<g's device, or the pipeline's without one>,
+        dtype=float32)`` — with one request per call the reference's order of use.  The reference draws them in fp16, the UNet's dtype; they are
+        fp32 here, as the latents are.  A resumed stage-2 call still draws all S.  The engine holds every step's noise of the call in ``eng.z``
+        (S, 2n, C, H/8, W/8) fp32, which captured graphs point at (S = 50, n = 8 at 1024²: 210 MB).  ``dedup`` falls back to the full batch (the two
+        samples of a request get different noise), a ``StageCache`` key also holds the generator's state in front of the noise draws (the noise
+        itself without a generator), ``concept_shard`` is refused (the ranks would have to agree on the noise), and a callback that replaces
+        ``latents`` leaves the noise as drawn."""
         dev, dt = self.unet.device, self.unet.dtype
         n = len(requests)
         height = height or self.unet.config.sample_size * self.vae_scale_factor
@@ -488,7 +498,9 @@ class LoraMultiConceptPipeline:
         if len(cn_keep[0]) != max(1, n_cn):
             raise ValueError(f"control_guidance_start / _end must be scalars or hold one entry per ControlNet ({max(1, n_cn)})")
         # ---- per-request tensors
+        stochastic = is_stochastic(self.scheduler, eta)      # omg_fuse_cfg_step_noise + the per-step noise eng.z
         lats, ehs_l, text_l, masks_l, cehs_l, ctext_l, ip_l, kps_l = [], [], [], [], [], [], [], []
+        z_l, zid_l = [], []                                    # stochastic: per request the (S, 2, C, H, W) noise and what identifies it
         active = None
         for r in requests:
             pe, ne = r["prompt_embeds"], r["negative_prompt_embeds"]
@@ -496,6 +508,12 @@ class LoraMultiConceptPipeline:
                 raise ValueError("prompt_embeds must hold the 2 global prompts [p, p] (lora_pipeline.py:291)")
             lat0 = self.prepare_latents(1, Cl, height, width, torch.float32, dev, r.get("generator"), r.get("latents"))
             lats.append(torch.cat([lat0, lat0.clone()]))                                            # duplicated x2 (:409)
+            if stochastic:      # then one (2, C, H/8, W/8) draw per step, one at a time (a single (S, 2, ...) draw gives other numbers)
+                g = r.get("generator")
+                z_id = g.get_state() if g is not None else None
+                zs = [draw_noise((2,) + tuple(lat0.shape[1:]), g, dev) for _ in range(S)]
+                z_l.append(torch.stack(zs))
+                zid_l.append(z_id if z_id is not None else z_l[-1])
             ehs_l.append(torch.cat([ne, pe], dim=0).to(device=dev, dtype=dt))                       # CFG order [neg, pos] (:467-474)
             text_l.append(torch.cat([r["negative_pooled_prompt_embeds"], r["pooled_prompt_embeds"]], dim=0).to(device=dev, dtype=dt))
             rpe = r.get("region_prompt_embeds") or []
@@ -524,6 +542,9 @@ class LoraMultiConceptPipeline:
                     kps_l.append(r["kps_image"].to(device=dev, dtype=torch.float32))
         Ka = len(active)
         shard = concept_shard if (concept_shard is not None and concept_shard.world > 1) else None
+        if shard is not None and stochastic:
+            raise L.OmgHipError("concept_shard with a stochastic step (Euler-ancestral, DDIM eta > 0) is not built: the ranks would have to agree "
+                                "on the noise; run the unsharded call")
         has_cb = callback is not None or callback_on_step_end is not None
         if has_cb:
             if shard is not None:
@@ -538,7 +559,8 @@ class LoraMultiConceptPipeline:
             if shard is not None:
                 raise L.OmgHipError("concept_shard with a list of ControlNets / guess_mode is not built: run the unsharded call")
             dedup, stage_cache, drop_unc0 = False, None, False        # the general ControlNet path runs the full batch
-        twin = bool(dedup) and shard is None and (controller is None or getattr(controller, "is_pure_replacement", False))
+        # a stochastic step gives the two samples of a request different noise from step 0: they are never the same computation
+        twin = bool(dedup) and shard is None and not stochastic and (controller is None or getattr(controller, "is_pure_replacement", False))
         if twin and controlnet is not None and controlnet_image is not None and controlnet_image.shape[0] not in (1, n):
             twin = False      # one conditioning image per MAIN ROW (4n): the two samples of a request may differ, and the 2n-row twin batch
                               # would not divide it — full batch instead
@@ -626,6 +648,8 @@ class LoraMultiConceptPipeline:
         # front of the engine because a resumed call without `unc0` runs a different row plan
         first = 0
         multistep = isinstance(self.scheduler, DPMSolverMultistepScheduler)    # omg_fuse_cfg_step_ms + the history buffer eng.x0_hist
+        # DDIM's table depends on eta (column 3: the noise coefficient); eta = 0 is the deterministic table, byte for byte
+        coef_now = self.scheduler.coef_table(dev, eta=eta) if isinstance(self.scheduler, DDIMScheduler) else self.scheduler.coef_table(dev)
         cache_keys: List[str] = []
         cache_hit = None
         base_traj = None                      # drop_unc0: per step k the (n, C, H, W) latents / model inputs of the base samples
@@ -643,10 +667,11 @@ class LoraMultiConceptPipeline:
                                                        getattr(controller, "num_self_replace", None)),
                       None if not use_cn else (id(controlnet), getattr(controlnet, "weights_version", 0), float(controlnet_conditioning_scale),
                                                tuple(k[0] for k in cn_keep[: fusion_start + 1])))
-            coef_key = self.scheduler.coef_table(dev)
+            coef_key = coef_now
             for j in range(n):
                 cn_img = None if not use_cn else (controlnet_image if controlnet_image.shape[0] == 1 else controlnet_image[j: j + 1])
-                cache_keys.append(StageCache.digest(common, coef_key, lats[j], ehs_l[j], text_l[j], cn_img))
+                z_key = (zid_l[j],) if stochastic else ()        # a trajectory is valid for the same noise only
+                cache_keys.append(StageCache.digest(common, coef_key, lats[j], ehs_l[j], text_l[j], cn_img, *z_key))
             hit = [stage_cache.get(k) for k in cache_keys]
             if multistep:      # the first resumed step also reads the data prediction of the step in front of it
                 hist_hit = [stage_cache.get_history(k) for k in cache_keys]
@@ -671,7 +696,7 @@ class LoraMultiConceptPipeline:
                str(dt), batched, bool(styleL), tuple(main_adapters), tuple(concept_adapters), float(concept_adapter_scale), main_scale,
                tuple(lora_list), mshape, tuple(ehs.shape), id(controller), id(controlnet), id(identitynet),
                float(controlnet_conditioning_scale), float(identitynet_conditioning_scale), twin,
-               (shard.rank, shard.world) if shard is not None else None, drop0,
+               (shard.rank, shard.world) if shard is not None else None, drop0, stochastic,
                None if cn_multi is None else (tuple(id(x) for x in cn_multi.nets), tuple(tuple(im.shape) for im in cn_multi.images), cn_multi.guess))
         eng = self._engines.pop(key, None)
         if eng is not None:
@@ -685,6 +710,8 @@ class LoraMultiConceptPipeline:
             eng.step_idx = torch.zeros(1, dtype=torch.int32, device=dev)
             if multistep:      # the previous step's data prediction of every sample (captured graphs point at it); order-1 steps do not read it
                 eng.x0_hist = torch.zeros((2 * n, Cl, Hl, Wl), dtype=torch.float32, device=dev)
+            if stochastic:     # every step's noise of every sample (captured graphs point at it), refilled in place per call
+                eng.z = torch.empty((S, 2 * n, Cl, Hl, Wl), dtype=torch.float32, device=dev)
             eng.ehs = torch.empty_like(ehs)
             eng.emb_main = torch.empty((S, nm, D), dtype=dt, device=dev)
             eng.emb_cur_main = torch.empty((nm, D), dtype=dt, device=dev)
@@ -767,12 +794,15 @@ class LoraMultiConceptPipeline:
         lat.copy_(torch.cat(lats, dim=0))
         eng.ehs.copy_(ehs)
         eng.emb_main.copy_(emb_main)
-        coef_now = self.scheduler.coef_table(dev)          # per call: the key holds the scheduler's class and step count, not its
+        # coef_now (above), per call: the key holds the scheduler's class and step count, not its
         if eng.coef is None:                               # configuration — a re-configured scheduler must not meet a cached table
             eng.coef = coef_now.clone()                    # the engine's OWN buffer: the scheduler's cached table is shared and read-only
         else:
             eng.coef.copy_(coef_now)                       # in place: captured graphs keep the pointer
         eng.step_idx.zero_()
+        if stochastic:
+            for j in range(n):
+                eng.z[:, 2 * j: 2 * j + 2].copy_(z_l[j])
         for j in range(n):
             for c in active:
                 eng.masks[j][c].copy_(masks_l[j][c])
@@ -996,8 +1026,12 @@ class LoraMultiConceptPipeline:
 
         def scheduler_step(j: int, **kw):
             """request j's fusion + CFG + scheduler update + next model input: the one-step linear table (DDIM, Euler) or the
-            multistep one with the request's rows of the history buffer (DPM-Solver++)"""
-            if multistep:
+            multistep one with the request's rows of the history buffer (DPM-Solver++), or the one-step table plus the request's
+            noise (Euler-ancestral, DDIM eta > 0)"""
+            if stochastic:
+                ops.fuse_cfg_step_noise(nout[4 * j: 4 * j + 4], lat[2 * j: 2 * j + 2], coef, eng.z[:, 2 * j: 2 * j + 2], step_idx,
+                                        guidance_scale=guidance_scale, model_input_next=xin[4 * j: 4 * j + 4], **kw)
+            elif multistep:
                 ops.fuse_cfg_step_ms(nout[4 * j: 4 * j + 4], lat[2 * j: 2 * j + 2], coef, eng.x0_hist[2 * j: 2 * j + 2], step_idx,
                                      guidance_scale=guidance_scale, model_input_next=xin[4 * j: 4 * j + 4], **kw)
             else:
@@ -1142,8 +1176,6 @@ class InstantidMultiConceptPipeline(LoraMultiConceptPipeline):
         if prompt_embeds is None:
             raise L.OmgHipError("pass prompt_embeds=/pooled_prompt_embeds= (text encoders are outside this package's scope)")
         stage_cache = kwargs.pop("stage_cache", None)
-        if eta != 0.0:
-            raise L.OmgHipError("eta != 0 (stochastic DDIM) is not used by OMG and is not supported")
         if guess_mode:
             # the reference's OWN InstantID loop cannot run it: the IdentityNet is fed the two concept rows and its residuals are then concatenated with
             # zeros to FOUR rows for a two-row concept UNet (instantid_pipeline.py:638-657), and the t2i net's two-row residuals meet the four-row main
@@ -1177,7 +1209,7 @@ class InstantidMultiConceptPipeline(LoraMultiConceptPipeline):
                                  stage_cache=stage_cache, original_size=original_size, crops_coords_top_left=crops_coords_top_left,
                                  target_size=target_size, control_guidance_start=control_guidance_start, control_guidance_end=control_guidance_end,
                                  negative_original_size=neg_cond[0], negative_crops_coords_top_left=neg_cond[1], negative_target_size=neg_cond[2],
-                                 **callbacks)[0]
+                                 eta=eta, **callbacks)[0]
         if trajectory is not None:
             trajectory.extend(t[0] for t in traj_many)
         lat = self._postprocess(lat, output_type)

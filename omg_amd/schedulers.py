@@ -21,6 +21,10 @@ would run Euler — both are provided, DDIM is the benc
 DPM-Solver++ (``DPMSolverMultistepScheduler``, the InstantID scripts' import) is not a one-step map: order 2 also reads the previous
 step's data prediction.  It exports an (n_steps, 8) table (:func:`dpm_coefficients`) for ``omg_fuse_cfg_step_ms``, which keeps that
 prediction in a device history buffer; see the class for the algorithm and the schedule choices it makes.
+
+Stochastic steps (``EulerAncestralDiscreteScheduler``; ``DDIMScheduler`` with eta > 0) are the same one-step map plus cz[i] * z_i, z_i
+fresh Gaussian noise the host draws from the caller's generator: column 3 of the (n_steps, 4) table holds cz, read by
+``omg_fuse_cfg_step_noise`` together with the pre-drawn noise of every step.
 """
 from __future__ import annotations
 
@@ -72,11 +76,17 @@ class _Base:
         """(n, 4) fp32 per-step coefficients [c_x, c_eps, c_in of the NEXT step, 0] on ``device``.  Cached per device, keyed by the BYTES of
         the host table: a re-configured scheduler (other betas / spacing / step count) gets a new table, an unchanged one costs no
         host-to-device copy per call (the table was rebuilt and copied on every pipeline call)."""
+        return self._table(device, self.cx, self.ce)
+
+    def _table(self, device, cx, ce, cz=None) -> torch.Tensor:
+        """the (n, 4) table of :meth:`coef_table` with column 3 = ``cz``, the noise coefficient of a stochastic step (0 when None)"""
         n = self.num_inference_steps
         tab = np.zeros((n, 4), dtype=np.float64)
-        tab[:, 0], tab[:, 1] = self.cx, self.ce
+        tab[:, 0], tab[:, 1] = cx, ce
         tab[:-1, 2] = self.cin[1:]
         tab[-1, 2] = 1.0
+        if cz is not None:
+            tab[:, 3] = cz
         host = tab.astype(np.float32)
         key = (str(device), host.tobytes())
         cached = self.__dict__.get("_coef_cache")
@@ -106,6 +116,14 @@ class _Base:
 
 
 class DDIMScheduler(_Base):
+    """DDIM; ``eta`` is an argument of :meth:`coef_table` and :meth:`step`, not configuration, as in diffusers (where it is a ``step()``
+    argument).  With eta > 0 the step adds std_i * z_i, z_i fresh Gaussian noise (formulas recalled from diffusers 0.25's
+    ``DDIMScheduler.step`` / ``_get_variance``, not checked against its source; parity stays unpinned):
+
+        std_i  = eta * sqrt((1 - a_prev) / (1 - a_t) * (1 - a_t / a_prev))
+        x'     = sqrt(a_prev / a_t) x + (sqrt(1 - a_prev - std_i^2) - sqrt(a_prev (1 - a_t) / a_t)) eps + std_i z_i
+
+    ``use_clipped_model_output`` is not built."""
     float_timesteps = False
     init_noise_sigma = 1.0
 
@@ -116,9 +134,39 @@ class DDIMScheduler(_Base):
         a_t = ac[self._ts]
         prev = self._ts - ratio
         a_p = np.where(prev >= 0, ac[np.clip(prev, 0, None)], ac[0])     # set_alpha_to_one = False
+        self._a_t, self._a_p = a_t, a_p
         self.cx = np.sqrt(a_p / a_t)
         self.ce = np.sqrt(1 - a_p) - np.sqrt(a_p * (1 - a_t) / a_t)
         self.cin = np.ones(n)
+
+    def eta_coefficients(self, eta: float):
+        """float64 (cx, ce, cz) per step for ``eta``; eta = 0 gives (cx, ce, 0) of the deterministic table"""
+        a_t, a_p = self._a_t, self._a_p
+        std = float(eta) * np.sqrt((1 - a_p) / (1 - a_t) * (1 - a_t / a_p))
+        ce = np.sqrt(1 - a_p - std ** 2) - np.sqrt(a_p * (1 - a_t) / a_t)
+        return self.cx, ce, std
+
+    def coef_table(self, device, eta: float = 0.0) -> torch.Tensor:
+        """(n, 4) fp32 table; eta = 0: exactly the deterministic table, eta > 0: row i = (cx_i, ce_i(eta), 1, std_i) for
+        ``omg_fuse_cfg_step_noise``"""
+        if float(eta) == 0.0:
+            return super().coef_table(device)
+        if float(eta) < 0.0:
+            raise ValueError(f"DDIMScheduler: eta={eta} must be >= 0")
+        return self._table(device, *self.eta_coefficients(eta))
+
+    def step(self, model_output: torch.Tensor, t, sample: torch.Tensor, eta: float = 0.0, use_clipped_model_output: bool = False,
+             generator=None, return_dict: bool = False, **kw):
+        """diffusers-style step; eta > 0 draws z = ``torch.randn`` (float32, on the generator's device) from ``generator``"""
+        if use_clipped_model_output:
+            raise L.OmgHipError("DDIMScheduler: use_clipped_model_output=True is not implemented")
+        if float(eta) == 0.0:
+            return super().step(model_output, t, sample)
+        i = self._index(t)
+        cx, ce, cz = (float(c[i]) for c in self.eta_coefficients(eta))
+        z = draw_noise(model_output.shape, generator, model_output.device)
+        prev = cx * sample.double() + ce * model_output.double() + cz * z.double()
+        return (prev.to(sample.dtype),)
 
 
 class EulerDiscreteScheduler(_Base):
@@ -334,5 +382,103 @@ class DPMSolverMultistepScheduler:
         return (prev.to(sample.dtype),)
 
 
+# ------------------------------------------------------------------------------------------------------- stochastic steps
+def draw_noise(shape, generator, device) -> torch.Tensor:
+    """one step's Gaussian noise: ``torch.randn(shape)`` float32 from ``generator`` on the generator's device (``device`` without one),
+    moved to ``device``.  diffusers draws it in the model output's dtype (fp16 in the reference's loop); float32 here, as for the initial
+    latents, so the numbers differ from an fp16 draw of the same generator."""
+    gen_dev = generator.device if generator is not None else device
+    return torch.randn(tuple(shape), generator=generator, device=gen_dev, dtype=torch.float32).to(device)
+
+
+# the keys of diffusers 0.25's EulerAncestralDiscreteScheduler.__init__ (recalled) with SDXL-base's schedule as the defaults, like _DPM_DEFAULTS
+_EULER_A_DEFAULTS = dict(num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", trained_betas=None,
+                         prediction_type="epsilon", timestep_spacing="leading", steps_offset=1, rescale_betas_zero_snr=False)
+_EULER_A_SUPPORTED = dict(beta_schedule=("linear", "scaled_linear"), trained_betas=(None,), prediction_type=("epsilon",),
+                          timestep_spacing=("leading",), rescale_betas_zero_snr=(False,))
+
+
+class EulerAncestralDiscreteScheduler(_Base):
+    """Euler-ancestral for epsilon prediction, after diffusers 0.25's ``EulerAncestralDiscreteScheduler`` (the usual SDXL sampler).  Per
+    step i, with sigma_from = sigma_i, sigma_to = sigma_{i+1} (0 after the last step):
+
+        sigma_up   = sqrt(sigma_to^2 (sigma_from^2 - sigma_to^2) / sigma_from^2),   sigma_down = sqrt(sigma_to^2 - sigma_up^2)
+        x'         = x + (sigma_down - sigma_i) eps + sigma_up z_i
+
+    z_i fresh Gaussian noise per step.  Table row i = (1, sigma_down - sigma_i, cin_{i+1}, sigma_up), read by ``omg_fuse_cfg_step_noise``;
+    the last step has sigma_up = 0 and adds no noise.  The schedule is EulerDiscreteScheduler's: "leading" timesteps, sigma interpolated at
+    them, cin = 1 / sqrt(sigma^2 + 1), init_noise_sigma = sqrt(max sigma^2 + 1).
+
+    Supported: epsilon prediction, "leading" spacing, steps_offset, a "linear" or "scaled_linear" beta schedule; any other value of a
+    diffusers option raises OmgHipError naming it.  The option names, the formulas and the schedule are recalled from diffusers 0.25, not
+    checked against its source: parity stays UNPINNED, as for the other schedulers.  The host ``step()`` is stateful like
+    diffusers' (the first call finds its step from ``t``) and draws its noise with :func:`draw_noise`."""
+    float_timesteps = True
+
+    def __init__(self, **kwargs):
+        unknown = sorted(set(kwargs) - set(_EULER_A_DEFAULTS))
+        if unknown:
+            raise TypeError(f"EulerAncestralDiscreteScheduler: unexpected keyword argument(s) {unknown}")
+        cfg = {**_EULER_A_DEFAULTS, **kwargs}
+        for name, ok in _EULER_A_SUPPORTED.items():
+            if cfg[name] not in ok:
+                raise L.OmgHipError(f"EulerAncestralDiscreteScheduler: {name}={cfg[name]!r} is not implemented; supported: {list(ok)}")
+        self._config = {"_class_name": type(self).__name__, **cfg}
+        T = self.num_train_timesteps = int(cfg["num_train_timesteps"])
+        if cfg["beta_schedule"] == "scaled_linear":
+            betas = np.linspace(cfg["beta_start"] ** 0.5, cfg["beta_end"] ** 0.5, T, dtype=np.float64) ** 2
+        else:
+            betas = np.linspace(cfg["beta_start"], cfg["beta_end"], T, dtype=np.float64)
+        self.alphas_cumprod = np.cumprod(1.0 - betas)
+        self.steps_offset = int(cfg["steps_offset"])
+        self.timesteps = None
+        self.num_inference_steps = None
+
+    @classmethod
+    def from_config(cls, config: Mapping, **overrides) -> "EulerAncestralDiscreteScheduler":
+        """diffusers' ``from_config``: the keys of ``config`` this scheduler has, then ``overrides``; other keys are ignored"""
+        merged = {**dict(config), **overrides}
+        return cls(**{k: v for k, v in merged.items() if k in _EULER_A_DEFAULTS})
+
+    def _build(self):
+        n = self.num_inference_steps
+        ac = self.alphas_cumprod
+        sig_all = np.sqrt((1 - ac) / ac)
+        s = np.interp(self._ts.astype(np.float64), np.arange(self.num_train_timesteps), sig_all)
+        self.sigmas = np.concatenate([s, [0.0]])
+        self.init_noise_sigma = float(np.sqrt(self.sigmas.max() ** 2 + 1))   # "leading" spacing
+        s_from, s_to = self.sigmas[:-1], self.sigmas[1:]
+        self.sigma_up = np.sqrt(s_to ** 2 * (s_from ** 2 - s_to ** 2) / s_from ** 2)
+        self.sigma_down = np.sqrt(s_to ** 2 - self.sigma_up ** 2)
+        self.cx = np.ones(n)
+        self.ce = self.sigma_down - s_from
+        self.cz = self.sigma_up
+        self.cin = 1.0 / np.sqrt(s ** 2 + 1)
+        self._step_index = None
+
+    def coef_table(self, device) -> torch.Tensor:
+        """(n, 4) fp32 table (1, sigma_down - sigma_i, cin_{i+1}, sigma_up), cached like ``_Base.coef_table``"""
+        return self._table(device, self.cx, self.ce, self.cz)
+
+    def step(self, model_output: torch.Tensor, t, sample: torch.Tensor, generator=None, return_dict: bool = False, **kw):
+        """diffusers-style STATEFUL step (reset by ``set_timesteps``): x + (sigma_down - sigma) eps + sigma_up z, z from ``generator``"""
+        if self._step_index is None:
+            self._step_index = self._index(t)
+        i = self._step_index
+        if i >= self.num_inference_steps:
+            raise ValueError("step() called more often than there are steps; call set_timesteps() again")
+        z = draw_noise(model_output.shape, generator, model_output.device)
+        prev = sample.double() + float(self.ce[i]) * model_output.double() + float(self.cz[i]) * z.double()
+        self._step_index = i + 1
+        return (prev.to(sample.dtype),)
+
+
+def is_stochastic(scheduler, eta: float = 0.0) -> bool:
+    """whether a step of ``scheduler`` adds fresh noise: Euler-ancestral always, DDIM when eta > 0; every other scheduler ignores eta
+    (as diffusers' ``prepare_extra_step_kwargs`` passes eta only to a ``step()`` that takes it)"""
+    return isinstance(scheduler, EulerAncestralDiscreteScheduler) or (isinstance(scheduler, DDIMScheduler) and float(eta) > 0.0)
+
+
 def make_scheduler(name: str):
-    return {"ddim": DDIMScheduler, "euler": EulerDiscreteScheduler, "dpm": DPMSolverMultistepScheduler}[name.lower()]()
+    return {"ddim": DDIMScheduler, "euler": EulerDiscreteScheduler, "dpm": DPMSolverMultistepScheduler,
+            "euler_a": EulerAncestralDiscreteScheduler}[name.lower()]()
