@@ -225,8 +225,9 @@ int omg_transpose_v(int dtype, const void* V, int64_t ldv, int64_t v_bstride,
                     int B, int heads, int Nkv, int Nkv_pad, void* Vt, int mfma_key_order, void* stream);
 
 /* ------------------------------------------------------------------------
- * Normalisation.  GroupNorm (NHWC, fp32 statistics, deterministic two-stage
- * reduction) replaces ResnetBlock2D.norm1/norm2 + nonlinearity, Transformer2D
+ * Normalisation.  GroupNorm (NHWC, fp32 statistics as sums shifted by a
+ * per-channel pivot and merged as (mean, M2), so that |mean| >> std does not
+ * cancel; deterministic two-stage reduction) replaces ResnetBlock2D.norm1/norm2 + nonlinearity, Transformer2D
  * .norm and UNet conv_norm_out + conv_act; LayerNorm replaces
  * BasicTransformerBlock.norm1/2/3 (diffusers 0.25.0 attention.py).
  * ---------------------------------------------------------------------- */

@@ -4,8 +4,8 @@
 // input gives bit-identical output on every run.
 //
 // GroupNorm is three launches: `gn_stats` writes per-(sample, pixel-chunk, group) partial
-// (sum, sumsq); `gn_finalize` folds the partials in a fixed order (in fp64) into
-// mean/rstd; `gn_apply` streams y = silu?(x*scale + shift).  The second read of x is served
+// (mean, M2) from sums shifted by a per-channel pivot; `gn_finalize` merges the partials in a
+// fixed order (in fp64) into mean/rstd; `gn_apply` streams y = silu?((x - mean)*scale + beta).  The second read of x is served
 // by L2 / Infinity Cache for every tensor on the SDXL path (<= 42 MB).
 #include "common.h"
 
@@ -30,90 +30,129 @@ OMG_DEV void gn_load(const GnP& p, int b, int pix, int vec, float (&f)[8]) {
   load8<T>(src, f);
 }
 
+// One element of [x1 | x2] as fp32 (the pivots of the statistics pass).
+template <typename T>
+OMG_DEV float gn_load1(const GnP& p, int b, int pix, int c) {
+  const T* src = (c < p.C1) ? (const T*)p.X1 + ((long)b * p.HW + pix) * p.C1 + c
+                            : (const T*)p.X2 + ((long)b * p.HW + pix) * p.C2 + (c - p.C1);
+  return (float)*src;
+}
+
+// Statistics of one pixel chunk.  The sums are SHIFTED: every channel c of the chunk has a pivot P_c, the median of the channel's
+// values at the chunk's first, middle and last pixel; a lane accumulates d = x - P_c and d * d in fp32, and the block turns them
+// into (mean, M2 = sum (x - mean)^2) per group.  Plain sum x / sum x^2 in fp32 lost var = E[x^2] - mean^2 to cancellation once
+// |mean| >> std (fp32 outputs off by 0.7 to 9 at mean / std = 1000).  The pivot is an element of the channel, so M2_c >= (P_c - mean_c)^2 and the
+// cancellation left in Q - S^2 / n is bounded by n * 2^-24 of M2_c whatever the pivot happens to be; the median keeps a single
+// outlier (a first pixel far from the rest) from being it, which would spend that bound.  The fold over rows and channels runs in
+// fp64 in a fixed order.
+// Workspace per (sample, chunk, group): {mean - P_bg, M2}, P_bg = the same median over the sample's first, middle and last pixel
+// at the first channel of the group: stored relative to an element of the group, the chunk mean keeps its precision in a float;
+// chunk 0 leaves P_bg in the (mean, rstd) slot for gn_finalize.
 template <typename T>
 __global__ __launch_bounds__(256) void gn_stats_kernel(GnP p) {
-  extern __shared__ float lds[];            // [pr][C] sums, then [pr][C] sumsq
+  extern __shared__ float lds[];            // [pr][C] shifted sums, [pr][C] shifted sums of squares, [C] pivots
   const int C = p.C1 + p.C2;
   const int tid = threadIdx.x;
   const int prow = tid / p.tpp, tv = tid - prow * p.tpp;
   const int chunk = blockIdx.x, b = p.b0 + blockIdx.y;
   const int pix0 = chunk * p.ppc;
   const int pix1 = min(p.HW, pix0 + p.ppc);
-  float s[2][8], q[2][8];
-#pragma unroll
-  for (int v = 0; v < 2; ++v)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { s[v][e] = 0.f; q[v][e] = 0.f; }
+  float* piv_s = lds + 2 * p.pr * C;
   if (prow < p.pr) {
-    // four pixels per trip: four independent 16-byte loads in flight per lane (one load per trip left the kernel latency-bound
-    // at 0.8-2 TB/s); the accumulation order over pixels is unchanged
-    for (int pix = pix0 + prow; pix < pix1; pix += 4 * p.pr) {
-#pragma unroll
-      for (int v = 0; v < 2; ++v) {
-        const int vec = tv + v * p.tpp;
-        if (v < p.vpt && vec < p.nvec) {
-          float f[4][8];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const int px = pix + u * p.pr;
-            if (px < pix1) gn_load<T>(p, b, px, vec, f[u]);
-            else {
-#pragma unroll
-              for (int e = 0; e < 8; ++e) f[u][e] = 0.f;
-            }
-          }
-#pragma unroll
-          for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { s[v][e] += f[u][e]; q[v][e] += f[u][e] * f[u][e]; }
-        }
-      }
-    }
-#pragma unroll
-    for (int v = 0; v < 2; ++v) {
+    // one of the lane's (at most two) channel vectors at a time: its sums and pivots are the only accumulators alive in the pixel loop
+    for (int v = 0; v < p.vpt; ++v) {
       const int vec = tv + v * p.tpp;
-      if (v < p.vpt && vec < p.nvec) {
+      if (vec >= p.nvec) break;
+      float s[8], q[8], pv[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          lds[prow * C + vec * 8 + e] = s[v][e];
-          lds[(p.pr + prow) * C + vec * 8 + e] = q[v][e];
+      for (int e = 0; e < 8; ++e) { s[e] = 0.f; q[e] = 0.f; }
+      {      // pivot: the median of the chunk's first, middle and last pixel — the same three cache lines for every pixel row
+        float pm[8], pl[8];
+        gn_load<T>(p, b, pix0, vec, pv);
+        gn_load<T>(p, b, (pix0 + pix1) >> 1, vec, pm);
+        gn_load<T>(p, b, pix1 - 1, vec, pl);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) pv[e] = __builtin_amdgcn_fmed3f(pv[e], pm[e], pl[e]);
+      }
+      // four pixels per trip: four independent 16-byte loads in flight per lane (one load per trip left the kernel latency-bound
+      // at 0.8-2 TB/s); the accumulation order over pixels is unchanged
+      for (int pix = pix0 + prow; pix < pix1; pix += 4 * p.pr) {
+        float f[4][8];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int px = pix + u * p.pr;
+          if (px < pix1) gn_load<T>(p, b, px, vec, f[u]);
+          else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) f[u][e] = pv[e];      // past the chunk: d = 0
+          }
         }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+          for (int e = 0; e < 8; ++e) { const float d = f[u][e] - pv[e]; s[e] += d; q[e] += d * d; }
+      }
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        lds[prow * C + vec * 8 + e] = s[e];
+        lds[(p.pr + prow) * C + vec * 8 + e] = q[e];
+        if (prow == 0) piv_s[vec * 8 + e] = pv[e];
       }
     }
   }
   __syncthreads();
   if (tid < p.G) {
-    float ss = 0.f, qq = 0.f;
-    for (int r = 0; r < p.pr; ++r)
-      for (int c = tid * p.cpg; c < (tid + 1) * p.cpg; ++c) { ss += lds[r * C + c]; qq += lds[(p.pr + r) * C + c]; }
+    const double npx = (double)(pix1 - pix0), inv = 1.0 / npx;
+    const double pbg = (double)__builtin_amdgcn_fmed3f(gn_load1<T>(p, b, 0, tid * p.cpg), gn_load1<T>(p, b, p.HW >> 1, tid * p.cpg), gn_load1<T>(p, b, p.HW - 1, tid * p.cpg));
+    // channel c: mean_c = P_c + S / n, M2_c = Q - S^2 / n; the group: M2 = sum_c M2_c + n * sum_c (mean_c - mean)^2, the second sum
+    // about the first channel's mean (r0) so that it does not cancel either
+    double r0 = 0.0, a1 = 0.0, a2 = 0.0, m2 = 0.0;
+    for (int c = tid * p.cpg; c < (tid + 1) * p.cpg; ++c) {
+      double ss = 0.0, qq = 0.0;
+      for (int r = 0; r < p.pr; ++r) { ss += (double)lds[r * C + c]; qq += (double)lds[(p.pr + r) * C + c]; }
+      const double dm = ((double)piv_s[c] - pbg) + ss * inv;
+      if (c == tid * p.cpg) r0 = dm;
+      const double e = dm - r0;
+      a1 += e; a2 += e * e;
+      m2 += qq - ss * ss * inv;
+    }
+    m2 += npx * (a2 - a1 * a1 / (double)p.cpg);
     float* out = p.ws + (((long)b * GN_MAX_CHUNKS + chunk) * p.G + tid) * 2;
-    out[0] = ss; out[1] = qq;
+    out[0] = (float)(r0 + a1 / (double)p.cpg);
+    out[1] = (float)(m2 > 0.0 ? m2 : 0.0);
+    if (chunk == 0) p.ws[(long)p.B * GN_MAX_CHUNKS * p.G * 2 + ((long)b * p.G + tid) * 2] = (float)pbg;
   }
 }
 
-// One wave per (group, sample): folds the chunk partials in a FIXED order (lane l takes chunks l, l + 64, ...; then a butterfly
-// whose pairing does not depend on the data) in fp64 and leaves (mean, rstd) behind the partials in the workspace.  Until round 2
+// One wave per (group, sample): merges the chunk partials {mean_k - P_bg, M2_k} (n_k = the chunk's pixels x channels per group) in a
+// FIXED order (lane l takes chunks l, l + 64, ...; then a butterfly whose pairing does not depend on the data) in fp64:
+//   mean = sum n_k mean_k / n,  M2 = sum M2_k + sum n_k (mean_k - mean)^2     (Chan et al.; the second sum about chunk 0's mean)
+// and leaves (mean, rstd) behind the partials in the workspace.  Until round 2
 // every block of gn_apply did this fold itself, 32 threads walking all the partials one dependent load after the other: with up to
 // 1024 chunks per sample that serial prologue was 80 % of the apply pass on the UNet's largest maps (4.6 ms for 4 GB of traffic).
 __global__ __launch_bounds__(64) void gn_finalize_kernel(GnP p) {
   const int g = blockIdx.x, b = p.b0 + blockIdx.y;
   const int lane = threadIdx.x;
-  double ss = 0.0, qq = 0.0;
+  const double r0 = (double)p.ws[(((long)b * GN_MAX_CHUNKS) * p.G + g) * 2];
+  double a1 = 0.0, a2 = 0.0, m2 = 0.0;
   for (int ch = lane; ch < p.nchunk; ch += 64) {
     const float* in = p.ws + (((long)b * GN_MAX_CHUNKS + ch) * p.G + g) * 2;
-    ss += (double)in[0]; qq += (double)in[1];
+    const double nk = (double)(min(p.HW, (ch + 1) * p.ppc) - ch * p.ppc) * p.cpg;
+    const double e = (double)in[0] - r0;
+    a1 += nk * e; a2 += nk * e * e; m2 += (double)in[1];
   }
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) {
-    ss += __shfl_xor(ss, o);
-    qq += __shfl_xor(qq, o);
+    a1 += __shfl_xor(a1, o);
+    a2 += __shfl_xor(a2, o);
+    m2 += __shfl_xor(m2, o);
   }
   if (lane == 0) {
     const double n = (double)p.HW * p.cpg;
-    const double mean = ss / n;
-    double var = qq / n - mean * mean;
-    if (var < 0.0) var = 0.0;
     float* mr = p.ws + (long)p.B * GN_MAX_CHUNKS * p.G * 2 + ((long)b * p.G + g) * 2;
+    const double mean = (double)mr[0] + r0 + a1 / n;      // mr[0]: P_bg, left by chunk 0 of gn_stats
+    double var = (m2 + (a2 - a1 * a1 / n)) / n;
+    if (var < 0.0) var = 0.0;
     mr[0] = (float)mean;
     mr[1] = (float)(1.0 / sqrt(var + (double)p.eps));
   }
@@ -137,85 +176,80 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(GnP p) {
   __syncthreads();
   const int prow = tid / p.tpp, tv = tid - prow * p.tpp;
   if (prow >= p.pr) return;
-  float sc[2][8], sh[2][8];
-#pragma unroll
-  for (int v = 0; v < 2; ++v) {
+  // y = (x - mean) * a + beta: x * a + (beta - mean * a) cancels a second time when |mean| >> std
+  const int pix0 = chunk * p.ppc;
+  const int pix1 = min(p.HW, pix0 + p.ppc);
+  // one of the lane's (at most two) channel vectors at a time: only its constants are alive in the pixel loop
+  for (int v = 0; v < p.vpt; ++v) {
     const int vec = tv + v * p.tpp;
-    if (v < p.vpt && vec < p.nvec) {
-      float ga[8], be[8];
+    if (vec >= p.nvec) break;
+    float sc[8], mu[8], sh[8];
+    {
+      float ga[8];
       load8<T>(p.gamma + (long)vec * 8 * sizeof(T), ga);
-      load8<T>(p.beta + (long)vec * 8 * sizeof(T), be);
+      load8<T>(p.beta + (long)vec * 8 * sizeof(T), sh);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         const int g = (vec * 8 + e) / p.cpg;
-        const float a = rstd_s[g] * ga[e];
-        sc[v][e] = a; sh[v][e] = be[e] - mean_s[g] * a;
+        sc[e] = rstd_s[g] * ga[e]; mu[e] = mean_s[g];
       }
     }
-  }
-  const int pix0 = chunk * p.ppc;
-  const int pix1 = min(p.HW, pix0 + p.ppc);
-  for (int pix = pix0 + prow; pix < pix1; pix += 4 * p.pr) {
+    for (int pix = pix0 + prow; pix < pix1; pix += 4 * p.pr) {
+      float f[4][8];
 #pragma unroll
-    for (int v = 0; v < 2; ++v) {
-      const int vec = tv + v * p.tpp;
-      if (v < p.vpt && vec < p.nvec) {
-        float f[4][8];
+      for (int u = 0; u < 4; ++u) {
+        const int px = pix + u * p.pr;
+        if (px < pix1) gn_load<T>(p, b, px, vec, f[u]);
+      }
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int px = pix + u * p.pr;
-          if (px < pix1) gn_load<T>(p, b, px, vec, f[u]);
-        }
+      for (int u = 0; u < 4; ++u) {
+        const int px = pix + u * p.pr;
+        if (px < pix1) {
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int px = pix + u * p.pr;
-          if (px < pix1) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              float y = f[u][e] * sc[v][e] + sh[v][e];
-              if (p.silu) y = silu_fast(y);
-              f[u][e] = y;
-            }
-            if constexpr (!MX8) store8<T>(p.Y + (((long)b * p.HW + px) * C + vec * 8) * (long)sizeof(T), f[u]);
+          for (int e = 0; e < 8; ++e) {
+            float y = (f[u][e] - mu[e]) * sc[e] + sh[e];
+            if (p.silu) y = silu_fast(y);
+            f[u][e] = y;
           }
+          if constexpr (!MX8) store8<T>(p.Y + (((long)b * p.HW + px) * C + vec * 8) * (long)sizeof(T), f[u]);
         }
-        if constexpr (MX8) {
-          // all four lanes of a 32-channel block share px (same prow) and take the same branches: the exchanges are safe
+      }
+      if constexpr (MX8) {
+        // all four lanes of a 32-channel block share px (same prow) and take the same branches: the exchanges are safe
 #pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const int px = pix + u * p.pr;
-            const bool ok = px < pix1;
-            float r[8];
-            {
-              const u32x4 pk = pack8<T>(f[u]);      // the value the 16-bit path would have stored
-              unpack8<T>(pk, r);
-            }
-            float amax = 0.f;
+        for (int u = 0; u < 4; ++u) {
+          const int px = pix + u * p.pr;
+          const bool ok = px < pix1;
+          float r[8];
+          {
+            const u32x4 pk = pack8<T>(f[u]);      // the value the 16-bit path would have stored
+            unpack8<T>(pk, r);
+          }
+          float amax = 0.f;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) amax = __builtin_fmaxf(amax, __builtin_fabsf(r[e]));
-            if (!ok) amax = 0.f;
-            amax = __builtin_fmaxf(amax, __shfl_xor(amax, 1));
-            amax = __builtin_fmaxf(amax, __shfl_xor(amax, 2));
-            const unsigned be = mx8_scale_exp(amax);
-            const float inv = mx8_inv_scale(be);
-            const int sc_mode = (C & 127) == 0 ? 2 : (C & 63) == 0 ? 1 : 0;
-            unsigned sc4 = be;                                   // every lane of the wave takes part in the exchanges
-            if (sc_mode >= 1) sc4 |= __shfl_down(be, 4) << 8;
-            if (sc_mode == 2) { sc4 |= __shfl_down(be, 8) << 16; sc4 |= __shfl_down(be, 12) << 24; }
-            if (ok) {
-              const long gp = (long)b * p.HW + px;
-              u32x2 o = {mx8_pack4(r[0] * inv, r[1] * inv, r[2] * inv, r[3] * inv), mx8_pack4(r[4] * inv, r[5] * inv, r[6] * inv, r[7] * inv)};
-              *(u32x2*)(p.Q + gp * p.Cq + vec * 8) = o;
-              // scale bytes: one store per 128 channels (C % 128 == 0: the four block exponents sit in lanes vec, +4, +8, +12 of the
-              // same pixel and wave), per 64 channels (C % 64 == 0), else per block — single-byte stores cost a transaction each
-              if (sc_mode == 2) { if ((vec & 15) == 0) *(unsigned*)(p.S + (((long)(vec >> 4) * p.P + gp) << 2)) = sc4; }
-              else if (sc_mode == 1) { if ((vec & 7) == 0) *(unsigned short*)(p.S + (((long)(vec >> 4) * p.P + gp) << 2) + ((vec >> 2) & 3)) = (unsigned short)sc4; }
-              else if ((vec & 3) == 0) p.S[(((long)(vec >> 4) * p.P + gp) << 2) + ((vec >> 2) & 3)] = (unsigned char)be;
-              const int cpad = C + vec * 8;      // the first (Cq - C) / 8 lanes of the pixel also clear its pad channels
-              if (cpad < p.Cq) {
-                *(u32x2*)(p.Q + gp * p.Cq + cpad) = u32x2{0u, 0u};
-                if ((cpad & 31) == 0) p.S[(((long)(cpad >> 7) * p.P + gp) << 2) + ((cpad >> 5) & 3)] = 0;
-              }
+          for (int e = 0; e < 8; ++e) amax = __builtin_fmaxf(amax, __builtin_fabsf(r[e]));
+          if (!ok) amax = 0.f;
+          amax = __builtin_fmaxf(amax, __shfl_xor(amax, 1));
+          amax = __builtin_fmaxf(amax, __shfl_xor(amax, 2));
+          const unsigned be = mx8_scale_exp(amax);
+          const float inv = mx8_inv_scale(be);
+          const int sc_mode = (C & 127) == 0 ? 2 : (C & 63) == 0 ? 1 : 0;
+          unsigned sc4 = be;                                   // every lane of the wave takes part in the exchanges
+          if (sc_mode >= 1) sc4 |= __shfl_down(be, 4) << 8;
+          if (sc_mode == 2) { sc4 |= __shfl_down(be, 8) << 16; sc4 |= __shfl_down(be, 12) << 24; }
+          if (ok) {
+            const long gp = (long)b * p.HW + px;
+            u32x2 o = {mx8_pack4(r[0] * inv, r[1] * inv, r[2] * inv, r[3] * inv), mx8_pack4(r[4] * inv, r[5] * inv, r[6] * inv, r[7] * inv)};
+            *(u32x2*)(p.Q + gp * p.Cq + vec * 8) = o;
+            // scale bytes: one store per 128 channels (C % 128 == 0: the four block exponents sit in lanes vec, +4, +8, +12 of the
+            // same pixel and wave), per 64 channels (C % 64 == 0), else per block — single-byte stores cost a transaction each
+            if (sc_mode == 2) { if ((vec & 15) == 0) *(unsigned*)(p.S + (((long)(vec >> 4) * p.P + gp) << 2)) = sc4; }
+            else if (sc_mode == 1) { if ((vec & 7) == 0) *(unsigned short*)(p.S + (((long)(vec >> 4) * p.P + gp) << 2) + ((vec >> 2) & 3)) = (unsigned short)sc4; }
+            else if ((vec & 3) == 0) p.S[(((long)(vec >> 4) * p.P + gp) << 2) + ((vec >> 2) & 3)] = (unsigned char)be;
+            const int cpad = C + vec * 8;      // the first (Cq - C) / 8 lanes of the pixel also clear its pad channels
+            if (cpad < p.Cq) {
+              *(u32x2*)(p.Q + gp * p.Cq + cpad) = u32x2{0u, 0u};
+              if ((cpad & 31) == 0) p.S[(((long)(cpad >> 7) * p.P + gp) << 2) + ((cpad >> 5) & 3)] = 0;
             }
           }
         }
@@ -410,7 +444,7 @@ int gn_run(int dtype, const void* X1, int C1, const void* X2, int C2, int B, int
   p.ws = workspace; p.Y = (char*)Y;
   p.Q = (char*)Q; p.S = (unsigned char*)S; p.P = (long)B * HW; p.Cq = (C + 127) / 128 * 128;
   hipStream_t s = (hipStream_t)stream;
-  const size_t lds = (size_t)2 * p.pr * C * sizeof(float);
+  const size_t lds = ((size_t)2 * p.pr + 1) * C * sizeof(float);      // <= 48 KiB (C <= 4096 has pr = 1)
   // one pair of launches for the whole batch.  Tried and rejected (round 2): statistics + apply on groups of samples sized to the
   // 256 MiB Infinity Cache so that the apply pass re-reads x on-die — 16 % SLOWER at B = 64 (smaller grids, 2 us per extra boundary).
   long sub = B;
