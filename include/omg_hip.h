@@ -274,6 +274,22 @@ typedef struct {
 } omg_conv2d_f32_args;
 
 int omg_conv2d_f32(const omg_conv2d_f32_args* a, void* stream);
+
+/* The same 3x3 / stride 1 / pad 1 convolution as Winograd F(2x2, 3x3): 16 instead of 36 multiplies per 2x2 output tile and input
+ * channel on the same MFMA (result equal to omg_conv2d_f32 to fp32 rounding, not bitwise).  U: the transformed weight G g G^T in
+ * the kernel's streaming order, fp32 [ceil(Cout / 64)][Cin / 8][pos 16][k chunk 2][row 64][4]  (element: position pos = 4 i + j of
+ * the 4x4 transform, output channel 64 block + row (zero beyond Cout), input channel 8 stage + 4 chunk + e);
+ * omg_conv2d_f32_wino_weight_floats gives its size.  Hout and Wout must be even. */
+typedef struct {
+  int32_t B, Hin, Win, Cin;   /* Cin % 8 == 0                                         */
+  int32_t Hout, Wout, Cout;   /* Hout = Hin (2 Hin with upsample), even; Cout % 4 == 0 */
+  int32_t upsample;           /* 1: nearest-2x upsample of X fused into the gather    */
+  const void* X; const void* U; const void* bias; const void* residual;   /* fp32; bias / residual may be NULL */
+  void* Y;                    /* [B, Hout, Wout, Cout] fp32                           */
+} omg_conv2d_f32_wino_args;
+
+int64_t omg_conv2d_f32_wino_weight_floats(int Cout, int Cin);
+int omg_conv2d_f32_wino(const omg_conv2d_f32_wino_args* a, void* stream);
 int omg_cast_f32(int dtype, const void* X, float* Y, int64_t n, void* stream);
 
 /* ------------------------------------------------------------------------

@@ -77,6 +77,14 @@ class Conv2dF32Args(C.Structure):
     ]
 
 
+class Conv2dF32WinoArgs(C.Structure):
+    _fields_ = [
+        ("B", c_i32), ("Hin", c_i32), ("Win", c_i32), ("Cin", c_i32),
+        ("Hout", c_i32), ("Wout", c_i32), ("Cout", c_i32), ("upsample", c_i32),
+        ("X", c_vp), ("U", c_vp), ("bias", c_vp), ("residual", c_vp), ("Y", c_vp),
+    ]
+
+
 class AttnArgs(C.Structure):
     _fields_ = [
         ("dtype", c_i32), ("B", c_i32), ("heads", c_i32), ("Nq", c_i32), ("Nkv", c_i32),
@@ -110,6 +118,8 @@ SYMBOLS = {
     "omg_groupnorm_mx8": (c_i32, [c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "omg_conv2d": (c_i32, [C.POINTER(Conv2dArgs), c_vp]),
     "omg_conv2d_f32": (c_i32, [C.POINTER(Conv2dF32Args), c_vp]),
+    "omg_conv2d_f32_wino_weight_floats": (c_i64, [c_i32, c_i32]),
+    "omg_conv2d_f32_wino": (c_i32, [C.POINTER(Conv2dF32WinoArgs), c_vp]),
     "omg_cast_f32": (c_i32, [c_i32, c_vp, c_vp, c_i64, c_vp]),
     "omg_attn_fwd": (c_i32, [C.POINTER(AttnArgs), c_vp]),
     "omg_transpose_v": (c_i32, [c_i32, c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp]),

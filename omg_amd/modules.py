@@ -225,6 +225,14 @@ class Conv2d(_Packed):
             self._packed["w"] = ops.pack_conv_weight(self.weight.data)
         return self._packed["w"]
 
+    def wino_weight(self) -> Optional[torch.Tensor]:
+        """Winograd F(2x2, 3x3) image of an fp32 3x3 weight (ops.conv2d_f32, algo "auto"); cached and invalidated like the packed weight."""
+        if self.ksize != 3 or self.stride != 1 or self.cin % 8 != 0 or self.weight.dtype != torch.float32:
+            return None
+        if "wu" not in self._packed:
+            self._packed["wu"] = ops.pack_conv_weight_wino(self.weight.data)
+        return self._packed["wu"]
+
     def mx8_ok(self) -> bool:
         """MX-fp8 eligibility: 3x3 / stride 1 on a 16-bit weight whose input channels are whole 32-element MX blocks."""
         return self.mx8 and self.ksize == 3 and self.stride == 1 and self.cin % 32 == 0 and self.weight.dtype != torch.float32
@@ -249,7 +257,8 @@ class Conv2d(_Packed):
         if self.weight.dtype == torch.float32:          # fp32 storage (the up blocks of the upcast VAE decode): f32-input MFMA kernel
             if x2 is not None or group_bias is not None or self.stride != 1:
                 raise L.OmgHipError("the fp32 convolution supports stride 1 without concat / per-sample bias (all the VAE decoder needs)")
-            return ops.conv2d_f32(x, self.packed_weight(), self.ksize, upsample=upsample, bias=self.bias, residual=residual)
+            return ops.conv2d_f32(x, self.packed_weight(), self.ksize, upsample=upsample, bias=self.bias, residual=residual,
+                                  wu=self.wino_weight())
         return ops.conv2d(x, self.packed_weight(), self.ksize, stride=self.stride, upsample=upsample, x2=x2, bias=self.bias,
                           group_bias=group_bias, residual=residual)
 

@@ -359,32 +359,64 @@ def conv2d_mx8(x: Mx8Map, w: "Mx8Tensor", *, bias: Optional[torch.Tensor] = None
     return y
 
 
+# which kernel the last conv2d_f32 call launched: "direct" (conv_f32_kernel) or "winograd" (conv_f32_wino_kernel)
+LAST_CONV2D_F32_ALGO: Optional[str] = None
+_F32_AUTO = {"winograd": True, "min_blocks": 256}
+
+
+def set_conv2d_f32_auto(winograd: bool = True, min_blocks: int = 256) -> None:
+    """What conv2d_f32(algo="auto") does: ``winograd=False`` keeps every launch on the direct kernel; ``min_blocks`` is the number of
+    Winograd workgroups from which a launch counts as filling the machine (256 CUs; 0: Winograd wherever it applies)."""
+    _F32_AUTO["winograd"], _F32_AUTO["min_blocks"] = bool(winograd), int(min_blocks)
+
+
 def conv2d_f32(x: torch.Tensor, w: torch.Tensor, ksize: int, *, upsample: bool = False, bias: Optional[torch.Tensor] = None,
-               residual: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """fp32 NHWC convolution on the f32-input MFMA (omg_conv2d_f32): the up blocks of the upcast VAE decode.
-    ``w``: fp32 [Cout, ksize*ksize*Cin] (pack_conv_weight of the fp32 OIHW tensor)."""
+               residual: Optional[torch.Tensor] = None, algo: str = "auto", wu: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 NHWC convolution on the f32-input MFMA: the up blocks of the upcast VAE decode.
+    ``w``: fp32 [Cout, ksize*ksize*Cin] (pack_conv_weight of the fp32 OIHW tensor).  ``wu``: the Winograd image of the same weight
+    (pack_conv_weight_wino).  ``algo``: "direct" = omg_conv2d_f32 (exact direct convolution), "winograd" = omg_conv2d_f32_wino
+    (F(2x2, 3x3); needs ``wu``, ksize 3, even output sizes, Cin % 8 == 0 — an error otherwise), "auto" = Winograd where it applies and
+    the launch fills the machine (at least one 16 x 16 x 64 block per CU), else direct."""
+    global LAST_CONV2D_F32_ALGO
     _dev(x)
     assert x.dtype == torch.float32 and w.dtype == torch.float32 and x.is_contiguous() and w.is_contiguous()
+    assert algo in ("auto", "direct", "winograd")
     B, Hin, Win, Cin = x.shape
     Cout = w.shape[0]
     assert w.shape[1] == ksize * ksize * Cin
     Ho, Wo = (2 * Hin, 2 * Win) if upsample else (Hin, Win)
+    wino_ok = ksize == 3 and Ho % 2 == 0 and Wo % 2 == 0 and Cin % 8 == 0 and wu is not None
+    if algo == "winograd" and not wino_ok:
+        raise L.OmgHipError("conv2d_f32(algo='winograd') needs ksize 3, even output sizes, Cin % 8 == 0 and the wu weight image")
+    use_wino = algo == "winograd" or (algo == "auto" and wino_ok and _F32_AUTO["winograd"]
+                                      and B * ((Ho + 15) // 16) * ((Wo + 15) // 16) * ((Cout + 63) // 64) >= _F32_AUTO["min_blocks"])
     y = torch.empty((B, Ho, Wo, Cout), dtype=torch.float32, device=x.device)
-    a = L.Conv2dF32Args()
-    a.B, a.Hin, a.Win, a.Cin, a.Hout, a.Wout, a.Cout, a.ksize, a.upsample = B, Hin, Win, Cin, Ho, Wo, Cout, ksize, int(upsample)
-    a.X, a.W, a.Y = x.data_ptr(), w.data_ptr(), y.data_ptr()
     if bias is not None:
         assert bias.dtype == torch.float32
-        a.bias = bias.data_ptr()
     if residual is not None:
         assert residual.dtype == torch.float32 and residual.is_contiguous() and residual.shape == y.shape
-        a.residual = residual.data_ptr()
+    if use_wino:
+        assert wu.dtype == torch.float32 and wu.is_contiguous() and wu.device == x.device
+        assert wu.numel() == L.lib().omg_conv2d_f32_wino_weight_floats(Cout, Cin)
+        a = L.Conv2dF32WinoArgs()
+        a.B, a.Hin, a.Win, a.Cin, a.Hout, a.Wout, a.Cout, a.upsample = B, Hin, Win, Cin, Ho, Wo, Cout, int(upsample)
+        a.X, a.U, a.Y = x.data_ptr(), wu.data_ptr(), y.data_ptr()
+        fn, name, tag = L.lib().omg_conv2d_f32_wino, "omg_conv2d_f32_wino", "conv_f32_wino"
+        flops = 2.0 * B * Ho * Wo * Cout * 4 * Cin          # executed matrix FLOPs: 16 products per 2x2 tile and (cin, cout) = 16/36 of direct
+    else:
+        a = L.Conv2dF32Args()
+        a.B, a.Hin, a.Win, a.Cin, a.Hout, a.Wout, a.Cout, a.ksize, a.upsample = B, Hin, Win, Cin, Ho, Wo, Cout, ksize, int(upsample)
+        a.X, a.W, a.Y = x.data_ptr(), w.data_ptr(), y.data_ptr()
+        fn, name, tag = L.lib().omg_conv2d_f32, "omg_conv2d_f32", "conv_f32"
+        flops = 2.0 * B * Ho * Wo * Cout * ksize * ksize * Cin
+    a.bias, a.residual = _p(bias), _p(residual)
+    LAST_CONV2D_F32_ALGO = "winograd" if use_wino else "direct"
     if _PROF is not None:
         t0 = _PROF.begin()
-        L.check(L.lib().omg_conv2d_f32(C.byref(a), _stream()), "omg_conv2d_f32")
-        _PROF.end("gemm_f32", 2.0 * B * Ho * Wo * Cout * ksize * ksize * Cin, t0, ("conv_f32", B * Ho * Wo, Cout, ksize * ksize * Cin, 0, 1, 0))
+        L.check(fn(C.byref(a), _stream()), name)
+        _PROF.end("gemm_f32", flops, t0, (tag, B * Ho * Wo, Cout, ksize * ksize * Cin, 0, 1, 0))
         return y
-    L.check(L.lib().omg_conv2d_f32(C.byref(a), _stream()), "omg_conv2d_f32")
+    L.check(fn(C.byref(a), _stream()), name)
     return y
 
 
@@ -768,6 +800,22 @@ def pack_conv_weight(w_oihw: torch.Tensor) -> torch.Tensor:
     """diffusers conv weight [Cout, Cin, kh, kw] -> [Cout, kh*kw*Cin] (K = (tap, cin)); pure layout."""
     co, ci, kh, kw = w_oihw.shape
     return w_oihw.permute(0, 2, 3, 1).reshape(co, kh * kw * ci).contiguous()
+
+
+def pack_conv_weight_wino(w_oihw: torch.Tensor) -> torch.Tensor:
+    """fp32 conv weight [Cout, Cin, 3, 3] -> the Winograd F(2x2, 3x3) image U = G g G^T that omg_conv2d_f32_wino streams:
+    [ceil(Cout / 64)][Cin / 8][pos 16][k chunk 2][row 64][4], zero rows beyond Cout.  Built once per weight."""
+    co, ci, kh, kw = w_oihw.shape
+    assert kh == 3 and kw == 3 and ci % 8 == 0 and w_oihw.dtype == torch.float32
+    def g_rows(t, dim):                                            # G t along ``dim``: [t0, (t0 + t1 + t2) / 2, (t0 - t1 + t2) / 2, t2], elementwise fp32
+        t0, t1, t2 = t.unbind(dim)
+        return torch.stack((t0, (t0 + t1 + t2) * 0.5, (t0 - t1 + t2) * 0.5, t2), dim)
+    u = g_rows(g_rows(w_oihw, 2), 3)                                # [Cout, Cin, 4, 4]
+    nb = (co + 63) // 64
+    up = torch.zeros((nb * 64, ci, 4, 4), dtype=torch.float32, device=w_oihw.device)
+    up[:co] = u
+    up = up.view(nb, 64, ci // 8, 2, 4, 16)                         # [nb][row][stage][chunk][e][pos]
+    return up.permute(0, 2, 5, 3, 1, 4).contiguous().view(-1)
 
 
 def pack_conv_in_weight(w_oihw: torch.Tensor) -> torch.Tensor:
