@@ -168,7 +168,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel2(AttnP p) {
     if (t == 0 || __builtin_amdgcn_ballot_w64(mt > ATTN_THR) != 0) {
       // raise (first tile: set) the reference: everything at the old reference is rescaled once, S' moves to the new one
       const float d = t == 0 ? mt : fmaxf(mt, 0.f);
-      const float alpha = __builtin_amdgcn_exp2f(-d);
+      const float alpha = t == 0 ? 1.f : __builtin_amdgcn_exp2f(-d);      // tile 0: O and l are still zero, and 2^-d is inf (0 * inf = NaN) where the row's first maximum is below -128
       m_ref += d;
       l_run *= alpha;
 #pragma unroll
@@ -350,7 +350,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel6(AttnP p, int q_chunk)
       if (t == 0 || __builtin_amdgcn_ballot_w64(mt > ATTN_THR) != 0) {
         // raise (first tile: set) the reference: everything at the old reference is rescaled once, S' moves to the new one
         const float d = t == 0 ? mt : fmaxf(mt, 0.f);
-        const float alpha = __builtin_amdgcn_exp2f(-d);
+        const float alpha = t == 0 ? 1.f : __builtin_amdgcn_exp2f(-d);      // tile 0: O and l are still zero, and 2^-d is inf (0 * inf = NaN) where the row's first maximum is below -128
         m_ref += d;
         l_run *= alpha;
 #pragma unroll

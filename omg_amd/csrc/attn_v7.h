@@ -254,7 +254,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel7(AttnP p, const char* 
       }
       if (t == 0 || __builtin_amdgcn_ballot_w64(mt > ATTN_THR) != 0) {
         const float d = t == 0 ? mt : fmaxf(mt, 0.f);
-        const float alpha = __builtin_amdgcn_exp2f(-d);
+        const float alpha = t == 0 ? 1.f : __builtin_amdgcn_exp2f(-d);      // tile 0: O and l are still zero, and 2^-d is inf (0 * inf = NaN) where the row's first maximum is below -128
         m_ref[qb] += d;
         if (t != 0) {      // what the matrix pipe has summed so far is at the old reference: fold it in before the sum is rescaled
           l_run[qb] += den16_read(den16[qb]);
@@ -327,20 +327,23 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel7(AttnP p, const char* 
     const float l_tot = l_run[qb] + den16_read(den16[qb]);
     const float inv = p.out_scale / l_tot;
     char* op = p.O + ((long)b * p.o_bs + (long)(qrow[qb] < p.Nq ? qrow[qb] : 0) * p.ldo + h * 64) * 2;
+    // the rounded output, ONCE for both store forms: written separately, hipcc rounded o * inv to fp16 in one step (v_fma_mixlo_f16) in one form and through
+    // fp32 (v_mul_f32 + v_cvt) in the other, and an fp16 output that was not 16-byte aligned differed from the aligned one in the last bit of about one
+    // element in 30000 (tests/test_attention_conditioning_gpu.py, section 4)
+    V4 pk[2][4];
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) pk[dt][g][e] = (T)(o[qb][dt][g * 4 + e] * inv);
     if (wide) {
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
         for (int g2 = 0; g2 < 2; ++g2) {
-          unsigned x[2], y[2];                      // the lane's packed pieces of groups 2 g2 and 2 g2 + 1
-#pragma unroll
-          for (int k = 0; k < 2; ++k) {
-            V4 pk;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) pk[e] = (T)(o[qb][dt][(2 * g2 + k) * 4 + e] * inv);
-            const u32x2 w2 = __builtin_bit_cast(u32x2, pk);
-            if (k == 0) { x[0] = w2[0]; x[1] = w2[1]; } else { y[0] = w2[0]; y[1] = w2[1]; }
-          }
+          const u32x2 wx = __builtin_bit_cast(u32x2, pk[dt][2 * g2]), wy = __builtin_bit_cast(u32x2, pk[dt][2 * g2 + 1]);
+          unsigned x[2] = {wx[0], wx[1]}, y[2] = {wy[0], wy[1]};      // the lane's packed pieces of groups 2 g2 and 2 g2 + 1
           // lanes 32..63 of x <-> lanes 0..31 of y: low half = [own x | partner's x] (d 8 g .. 8 g + 7), high half = [partner's y | own y] (g + 1)
           asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %2\n\tv_permlane32_swap_b32 %1, %3\n\ts_nop 1" : "+v"(x[0]), "+v"(x[1]), "+v"(y[0]), "+v"(y[1]));
           const u32x4 out = {x[0], x[1], y[0], y[1]};
@@ -352,18 +355,18 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel7(AttnP p, const char* 
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           const int d = dt * 32 + 8 * g + 4 * hi;
-          float v[4];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = o[qb][dt][g * 4 + e] * inv;
           V4* dst = (V4*)(op + d * 2);
+          V4 out = pk[dt][g];
           if (p.accumulate) {
-            V4 old = *dst;
+            const V4 old = *dst;
+            float v[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = o[qb][dt][g * 4 + e] * inv;
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] += (float)old[e];
-          }
-          V4 out;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) out[e] = (T)v[e];
+            for (int e = 0; e < 4; ++e) out[e] = (T)v[e];
+          }
           *dst = out;
         }
     }
