@@ -180,6 +180,37 @@ typedef struct {
 int omg_conv2d(const omg_conv2d_args* a, void* stream);
 
 /* ------------------------------------------------------------------------
+ * omg_conv2d_slots — omg_conv2d with a weight slot per sample and the LoRA
+ * second K-segment: LoRA on convolution layers (LoCon / PEFT Conv2d).
+ *
+ * The reference loads concept and style LoRAs with pipe.load_lora_weights
+ * (inference_lora.py:162-170, inference_instantid.py:220-222; diffusers 0.25 +
+ * peft 0.8.2), which wraps Conv2d layers as readily as Linear ones:
+ *   y = conv(x; W) + s * B(A(x)),  A: k x k conv Cin -> r with the base layer's
+ *   stride and padding, B: 1x1 conv r -> Cout  (peft tuners/lora/layer.py Conv2d),
+ * toggled per concept pass by set_adapters (lora_pipeline.py:340-342, :588-591).
+ * Semantics follow omg_gemm's: a sample is a group (rows_per_group = Hout*Wout),
+ * M tiles never straddle a sample.
+ *   merged mode : conv.W = [1+S][Cout][K] (base, then W + s*B_s A_s), w_slot_stride = Cout*K, K2 = 0.
+ *   segment mode: first the LoRA-down conv (conv.W = [S][r_pad][K], w_slot_stride = r_pad*K, Cout = r_pad; a sample whose
+ *                 slot is -1 is skipped and its output rows are left untouched), then the base conv with w_slot_stride = 0,
+ *                 A2 = the down result, W2 = [S][Cout][K2] = s*B: samples with slot >= 0 add A2 . W2[slot]^T into the SAME
+ *                 accumulator before the epilogue (acc + bias + group_bias) * out_scale + residual, with the activation.
+ * Without group_adapter every sample uses slot 0.  Slot values are read on the device and not range-checked.
+ * ---------------------------------------------------------------------- */
+typedef struct {
+  omg_conv2d_args conv;            /* exactly omg_conv2d's meaning                                  */
+  const int32_t* group_adapter;    /* [B] weight slot of each sample; NULL = slot 0                 */
+  int64_t w_slot_stride;           /* elements between weight slots of conv.W; 0 = one shared W     */
+  const void* A2; int64_t lda2;    /* [B*Hout*Wout, K2] LoRA-down result (16-bit), or NULL          */
+  const void* W2; int64_t ldw2;    /* [Cout, K2] per slot: s*B                                      */
+  int64_t w2_slot_stride;          /* elements between slots of W2; 0 = shared                      */
+  int32_t K2;                      /* K2 % 8 == 0; 0 disables the segment                           */
+} omg_conv2d_slots_args;
+
+int omg_conv2d_slots(const omg_conv2d_slots_args* a, void* stream);
+
+/* ------------------------------------------------------------------------
  * omg_attn_fwd — softmax(Q K^T * scale) V, head_dim 64, never materialising
  * the probabilities, with prompt-to-prompt "probability borrowing".
  *

@@ -69,6 +69,14 @@ class Conv2dArgs(C.Structure):
     ]
 
 
+class Conv2dSlotsArgs(C.Structure):
+    _fields_ = [
+        ("conv", Conv2dArgs), ("group_adapter", c_vp), ("w_slot_stride", c_i64),
+        ("A2", c_vp), ("lda2", c_i64), ("W2", c_vp), ("ldw2", c_i64),
+        ("w2_slot_stride", c_i64), ("K2", c_i32),
+    ]
+
+
 class Conv2dF32Args(C.Structure):
     _fields_ = [
         ("B", c_i32), ("Hin", c_i32), ("Win", c_i32), ("Cin", c_i32),
@@ -117,6 +125,7 @@ SYMBOLS = {
     "omg_conv2d_mx8": (c_i32, [C.POINTER(Conv2dMx8Args), c_vp]),
     "omg_groupnorm_mx8": (c_i32, [c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "omg_conv2d": (c_i32, [C.POINTER(Conv2dArgs), c_vp]),
+    "omg_conv2d_slots": (c_i32, [C.POINTER(Conv2dSlotsArgs), c_vp]),
     "omg_conv2d_f32": (c_i32, [C.POINTER(Conv2dF32Args), c_vp]),
     "omg_conv2d_f32_wino_weight_floats": (c_i64, [c_i32, c_i32]),
     "omg_conv2d_f32_wino": (c_i32, [C.POINTER(Conv2dF32WinoArgs), c_vp]),

@@ -151,8 +151,11 @@ OMG_DEV void gemm_epilogue(const GemmP& p, f32x16 (&acc)[2][2], char* smem, int 
   }
 }
 
-template <typename T, bool CONV, bool GLDS>
+// CSEG (CONV only): the launch may carry the LoRA second K-segment (omg_conv2d_slots): stages kt >= nk1 read plain A2 rows and W2p exactly
+// as the non-conv form does.  A separate instantiation, so that the conv kernels omg_conv2d launches keep their code.
+template <typename T, bool CONV, bool GLDS, bool CSEG = false>
 __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmP p) {
+  static_assert(CONV || !CSEG, "CSEG is the segment of the CONV form; the plain form always has it");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -234,7 +237,8 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmP p) {
     int dy = 0, dx = 0, c0 = k0;
     const char* xsrc = p.A; int xC = p.C1;
     if constexpr (CONV) {
-      const int tap = kt / cpt; const int cc = kt - tap * cpt;
+      const int ktc = (CSEG && s2) ? 0 : kt;                   // a segment stage decodes no tap
+      const int tap = ktc / cpt; const int cc = ktc - tap * cpt;
       dy = tap / p.ksize; dx = tap - dy * p.ksize;
       c0 = cc * BK;
       if (c0 >= p.C1) { xsrc = p.X2; xC = p.C2; c0 -= p.C1; }
@@ -255,6 +259,9 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmP p) {
         if (p.upsample) { iy >>= 1; ix >>= 1; }
         const long pix = ((long)cb[i] * p.Hin + iy) * p.Win + ix;
         asrc = ok ? xsrc + (pix * xC + c0 + c * 8) * 2 : zero;
+        if constexpr (CSEG) {
+          if (s2) asrc = kvalid ? p.A2 + ((long)arow[i] * p.lda2 + k0 + c * 8) * 2 : zero;
+        }
       } else {
         if (!s2) asrc = kvalid ? p.A + ((long)arow[i] * p.lda + k0 + c * 8) * 2 : zero;
         else     asrc = kvalid ? p.A2 + ((long)arow[i] * p.lda2 + a2off + k0 + c * 8) * 2 : zero;
@@ -966,6 +973,16 @@ int launch(const GemmP& p, hipStream_t s) {
   }
   const int grid = p.tile_groups * p.tiles_m * p.tiles_n;
   if (grid <= 0) return OMG_OK;
+  if constexpr (CONV) {
+    if (p.K2 > 0) {      // omg_conv2d_slots with the LoRA segment: the CONV form that reads A2 / W2 in its last stages
+      if (g_use_glds) {
+        OMG_LAUNCH((gemm_kernel<T, true, true, true>), dim3(grid), dim3(256), LDS_BYTES, s, p);
+      } else {
+        OMG_LAUNCH((gemm_kernel<T, true, false, true>), dim3(grid), dim3(256), LDS_BYTES, s, p);
+      }
+      return omg_check_launch("gemm");
+    }
+  }
   if (g_use_glds) {
     OMG_LAUNCH((gemm_kernel<T, CONV, true>), dim3(grid), dim3(256), LDS_BYTES, s, p);
   } else {
@@ -983,11 +1000,15 @@ void ensure_attrs() {
   (void)hipFuncSetAttribute((const void*)gemm_kernel<f16, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
   (void)hipFuncSetAttribute((const void*)gemm_kernel<f16, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
   (void)hipFuncSetAttribute((const void*)gemm_kernel<f16, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+  (void)hipFuncSetAttribute((const void*)gemm_kernel<f16, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+  (void)hipFuncSetAttribute((const void*)gemm_kernel<f16, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
 #ifndef OMG_DEV_F16_ONLY
   (void)hipFuncSetAttribute((const void*)gemm_kernel<bf16, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
   (void)hipFuncSetAttribute((const void*)gemm_kernel<bf16, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
   (void)hipFuncSetAttribute((const void*)gemm_kernel<bf16, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
   (void)hipFuncSetAttribute((const void*)gemm_kernel<bf16, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+  (void)hipFuncSetAttribute((const void*)gemm_kernel<bf16, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+  (void)hipFuncSetAttribute((const void*)gemm_kernel<bf16, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
 #endif
 }
 
@@ -1046,8 +1067,9 @@ extern "C" int omg_gemm(const omg_gemm_args* a, void* stream) {
 #endif
 }
 
-extern "C" int omg_conv2d(const omg_conv2d_args* a, void* stream) {
-  OMG_REQUIRE(a != nullptr, "omg_conv2d: null args");
+// validation + parameter block shared by omg_conv2d and omg_conv2d_slots, in omg_conv2d's order of checks (`p` is exactly what omg_conv2d
+// launches).  An empty batch leaves p.M == 0 and returns OMG_OK where omg_conv2d always did: before the act / ldgb / DEV-build checks.
+static int conv2d_params(const omg_conv2d_args* a, GemmP& p) {
   OMG_REQUIRE(a->dtype == OMG_F16 || a->dtype == OMG_BF16, "omg_conv2d: dtype");
   OMG_REQUIRE(a->ksize == 1 || a->ksize == 3, "omg_conv2d: ksize must be 1 or 3");
   OMG_REQUIRE(a->stride == 1 || a->stride == 2, "omg_conv2d: stride must be 1 or 2");
@@ -1060,7 +1082,6 @@ extern "C" int omg_conv2d(const omg_conv2d_args* a, void* stream) {
   OMG_REQUIRE(a->Hout == (Hl + 2 * pad - a->ksize) / a->stride + 1 && a->Wout == (Wl + 2 * pad - a->ksize) / a->stride + 1,
               "omg_conv2d: output size mismatch");
   ensure_attrs();
-  GemmP p{};
   const int Ctot = a->C1 + a->C2;
   p.M = a->B * a->Hout * a->Wout; p.N = a->Cout; p.K = a->ksize * a->ksize * Ctot;
   if (p.M == 0) return OMG_OK;
@@ -1075,11 +1096,57 @@ extern "C" int omg_conv2d(const omg_conv2d_args* a, void* stream) {
   p.ksize = a->ksize; p.stride = a->stride; p.upsample = a->upsample;
   p.tiles_m = (p.M + BM - 1) / BM; p.tiles_n = (p.N + BN - 1) / BN;
   if (a->group_bias) OMG_REQUIRE(a->ldgb % 8 == 0, "omg_conv2d: ldgb");
-  hipStream_t s = (hipStream_t)stream;
 #ifdef OMG_DEV_F16_ONLY
   OMG_REQUIRE(a->dtype == OMG_F16, "omg_conv2d: this is a DEV=1 build (fp16 kernels only)");
+#endif
+  return OMG_OK;
+}
+
+static int conv2d_launch(int dtype, const GemmP& p, hipStream_t s) {
+#ifdef OMG_DEV_F16_ONLY
+  (void)dtype;
   return launch<f16, true>(p, s);
 #else
-  return a->dtype == OMG_F16 ? launch<f16, true>(p, s) : launch<bf16, true>(p, s);
+  return dtype == OMG_F16 ? launch<f16, true>(p, s) : launch<bf16, true>(p, s);
 #endif
+}
+
+extern "C" int omg_conv2d(const omg_conv2d_args* a, void* stream) {
+  OMG_REQUIRE(a != nullptr, "omg_conv2d: null args");
+  GemmP p{};
+  const int rc = conv2d_params(a, p);
+  if (rc != OMG_OK || p.M == 0) return rc;
+  return conv2d_launch(a->dtype, p, (hipStream_t)stream);
+}
+
+// omg_conv2d with a weight slot per sample and the LoRA second K-segment (include/omg_hip.h).  A sample is a tile group
+// (rows_per_group = Hout * Wout, no M tile straddles two samples), so every tile has ONE weight base: the per-tile `Wp` / `rsW`
+// the tile kernels already compute for the Linear layers' slot GEMM.  Launches without a segment take the variant the chooser
+// picks for (Hout * Wout rows, B groups); a segment launch stays on the 128x128 kernel's CSEG form, as the Linear layers' does.
+extern "C" int omg_conv2d_slots(const omg_conv2d_slots_args* a, void* stream) {
+  OMG_REQUIRE(a != nullptr, "omg_conv2d_slots: null args");
+  OMG_REQUIRE(a->K2 >= 0 && a->K2 % 8 == 0, "omg_conv2d_slots: K2 must be a non-negative multiple of 8");
+  OMG_REQUIRE(a->w_slot_stride >= 0 && a->w_slot_stride % 8 == 0, "omg_conv2d_slots: w_slot_stride must be a non-negative multiple of 8");
+  if (a->K2 > 0) {
+    OMG_REQUIRE(a->A2 && a->W2, "omg_conv2d_slots: LoRA segment operands");
+    OMG_REQUIRE(a->lda2 >= a->K2 && a->lda2 % 8 == 0 && a->ldw2 >= a->K2 && a->ldw2 % 8 == 0,
+                "omg_conv2d_slots: lda2 / ldw2 must be multiples of 8 and at least K2");
+    OMG_REQUIRE(a->w2_slot_stride >= 0 && a->w2_slot_stride % 8 == 0, "omg_conv2d_slots: w2_slot_stride must be a non-negative multiple of 8");
+  }
+  GemmP p{};
+  const int rc = conv2d_params(&a->conv, p);
+  if (rc != OMG_OK) return rc;
+  OMG_REQUIRE(a->w_slot_stride == 0 || a->w_slot_stride >= (int64_t)p.N * p.K, "omg_conv2d_slots: w_slot_stride smaller than one weight");
+  if (p.M == 0) return OMG_OK;
+  const bool per_sample = a->group_adapter != nullptr && a->conv.B > 1;
+  if (per_sample) {
+    p.tile_groups = a->conv.B;
+    p.tiles_m = (p.rows_per_group + BM - 1) / BM;      // per group
+  }
+  p.group_adapter = a->group_adapter;
+  p.w_adapter_stride = a->w_slot_stride;
+  p.A2 = (const char*)a->A2; p.lda2 = a->lda2; p.W2 = (const char*)a->W2; p.ldw2 = a->ldw2;
+  p.K2 = a->K2; p.w2_adapter_stride = a->w2_slot_stride;
+  if (p.K2 == 0) { p.A2 = nullptr; p.W2 = nullptr; }
+  return conv2d_launch(a->conv.dtype, p, (hipStream_t)stream);
 }

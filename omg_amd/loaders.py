@@ -14,6 +14,10 @@ styles for the UNet part of a LoRA file:
                ``--lora_path``) — the SGM/ldm block naming ``input_blocks_4_1_...`` / ``middle_block_1_...`` /
                ``output_blocks_3_1_...``, remapped here as diffusers' ``_maybe_map_sgm_blocks_to_diffusers`` does [recalled].
 
+Convolution entries (kohya ``conv_dim``, LyCORIS "LoCon", PEFT ``target_modules`` naming ``conv1`` / ``conv2`` ...) come in the same
+three key styles with a 4-D down weight ``[r, Cin, k, k]`` and an up weight ``[Cout, r, 1, 1]``; ``load_lora_adapter`` accepts them
+for the convolutions of :func:`conv_module_paths`.  LoHa / LoKr / Tucker / DoRA files are refused by name.
+
 All are mapped onto the module paths of :class:`omg_amd.unet.UNet2DConditionModel` (whose state-dict keys equal
 diffusers', boundary B4) and returned as a :class:`omg_amd.lora.LoraAdapter`.  A per-layer ``alpha`` (kohya) is folded
 into the up matrix (``B <- B * alpha / r``); per-layer ranks may differ (PEFT ``rank_pattern``).  Text-encoder entries
@@ -32,7 +36,7 @@ from typing import Dict, Iterable, List, Optional, Tuple
 import torch
 
 from .lora import LoraAdapter
-from .modules import Linear
+from .modules import Linear, lora_conv_targets
 
 
 class LoaderError(ValueError):
@@ -132,6 +136,18 @@ def linear_module_paths(unet: torch.nn.Module) -> List[str]:
     return [n for n, m in unet.named_modules() if isinstance(m, Linear)]
 
 
+_CONV_BOUNDARY = ("conv_in", "conv_out")
+_CONV_BOUNDARY_FLAT = ("conv_in", "conv_out", "input_blocks_0_0", "out_2")          # the same two layers in kohya's flat / SGM names
+# other adapter algebras that share the lora_unet_* / PEFT namespaces (LyCORIS LoHa, LoKr, Tucker-decomposed LoCon, DoRA)
+_FOREIGN = ("hada_", "lokr_", "lora_mid", "dora_scale", "lora_magnitude_vector")
+
+
+def conv_module_paths(unet: torch.nn.Module) -> Dict[str, Tuple[int, int, int]]:
+    """``{module path: (Cin, Cout, k)}`` of the convolutions a LoRA may target: every 16-bit :class:`Conv2d` the slot kernel runs (resnet
+    conv1 / conv2 / conv_shortcut, ``downsamplers.0.conv``, ``upsamplers.0.conv``).  ``conv_in`` / ``conv_out`` are not targets."""
+    return {n: (m.cin, m.cout, m.ksize) for n, m in lora_conv_targets(unet).items()}
+
+
 _TE_PROJ = ("q_proj", "k_proj", "v_proj", "out_proj", "fc1", "fc2")
 
 
@@ -144,12 +160,22 @@ def _te_unflatten(flat: str) -> str:
 
 
 def parse_lora_state_dict(sd: Dict[str, torch.Tensor], module_paths: Iterable[str], name: str = "lora",
-                          layers_per_block: int = 2) -> Tuple[LoraAdapter, List[str]]:
+                          layers_per_block: int = 2,
+                          conv_paths: Optional[Dict[str, Tuple[int, int, int]]] = None) -> Tuple[LoraAdapter, List[str]]:
     """Key-style detection + mapping (see the module docstring).  Returns ``(adapter, skipped_keys)``; raises
-    ``LoaderError`` for a UNet entry that names no Linear layer of ``module_paths`` (conv LoRA is not supported by the
-    slot GEMM) or for a half-present pair.  ``skipped_keys`` lists what was neither UNet nor text-encoder material."""
+    ``LoaderError`` for a UNet entry that names no Linear layer of ``module_paths`` and no convolution of ``conv_paths``
+    (``{path: (Cin, Cout, k)}``, :func:`conv_module_paths`; ``None``: Linear targets only) or for a half-present pair.  With
+    ``conv_paths`` it also raises, by name, for a down kernel that is not the base layer's, an up weight that is not 1x1, an entry
+    for ``conv_in`` / ``conv_out`` and for LoHa / LoKr / Tucker / DoRA keys.  ``skipped_keys`` lists what was neither UNet nor
+    text-encoder material."""
     paths = set(module_paths)
-    flat = {p.replace(".", "_"): p for p in paths}
+    convs = dict(conv_paths or {})
+    flat = {p.replace(".", "_"): p for p in list(paths) + list(convs)}
+    if conv_paths is not None:
+        foreign = sorted(k for k in sd if any(f in k for f in _FOREIGN))
+        if foreign:
+            raise LoaderError(f"{foreign[0]!r}: LoHa / LoKr / Tucker (lora_mid) / DoRA entries are not plain LoRA pairs and are not "
+                              f"supported ({len(foreign)} such keys)")
     # key = ("unet", module) or ("te", 1 | 2, module)
     down: Dict[tuple, torch.Tensor] = {}
     up: Dict[tuple, torch.Tensor] = {}
@@ -159,9 +185,11 @@ def parse_lora_state_dict(sd: Dict[str, torch.Tensor], module_paths: Iterable[st
     def put(mod: str, which: str, t: torch.Tensor, key: str):
         if mod.endswith(".to_out") and mod + ".0" in paths:      # diffusers' Attention.to_out is [Linear, Dropout]
             mod = mod + ".0"
-        if mod not in paths:
+        if conv_paths is not None and mod in _CONV_BOUNDARY:
+            raise LoaderError(f"LoRA entry {key!r} targets {mod!r}: conv_in / conv_out are not LoRA targets")
+        if mod not in paths and mod not in convs:
             raise LoaderError(f"LoRA entry {key!r} targets {mod!r}, which is not a Linear layer of this UNet "
-                              f"(LoRA on conv layers is not supported)")
+                              + ("(LoRA on conv layers is not supported)" if conv_paths is None else "nor one of its LoRA-capable convolutions"))
         (down if which == "down" else up)[("unet", mod)] = t
 
     def put_te(n: int, mod: str, which: str, t: torch.Tensor):
@@ -201,6 +229,8 @@ def parse_lora_state_dict(sd: Dict[str, torch.Tensor], module_paths: Iterable[st
         m = _KOHYA.match(key)
         if m:
             mod = flat.get(m["flat"]) or flat.get(sgm_flat_to_diffusers_flat(m["flat"], layers_per_block))
+            if mod is None and conv_paths is not None and m["flat"] in _CONV_BOUNDARY_FLAT:
+                raise LoaderError(f"kohya LoRA entry {key!r} targets conv_in / conv_out, which are not LoRA targets")
             if mod is None:
                 raise LoaderError(f"kohya LoRA entry {key!r} matches no Linear layer of this UNet "
                                   f"(LoRA on conv layers is not supported)")
@@ -220,6 +250,20 @@ def parse_lora_state_dict(sd: Dict[str, torch.Tensor], module_paths: Iterable[st
     te: Dict[int, Dict[str, Tuple[torch.Tensor, torch.Tensor]]] = {}
     for k in sorted(down, key=str):
         a, b = down[k].float(), up[k].float()
+        if k[0] == "unet" and k[1] in convs:
+            cin, cout, ks = convs[k[1]]
+            if a.dim() != 4 or tuple(a.shape[1:]) != (cin, ks, ks):
+                raise LoaderError(f"conv LoRA down weight of {k[1]}: {tuple(a.shape)} is not [r, {cin}, {ks}, {ks}] — the down kernel must be "
+                                  f"the base layer's")
+            if b.dim() == 4 and tuple(b.shape[2:]) != (1, 1):
+                raise LoaderError(f"conv LoRA up weight of {k[1]}: {tuple(b.shape)} is not a 1x1 convolution")
+            if b.dim() not in (2, 4) or tuple(b.shape[:2]) != (cout, a.shape[0]):
+                raise LoaderError(f"LoRA shapes of {k}: down {tuple(a.shape)}, up {tuple(b.shape)}")
+            b = b.reshape(cout, a.shape[0])
+            if k in alpha:
+                b = b * (alpha[k] / a.shape[0])
+            weights[k[1]] = (a, b)
+            continue
         if a.dim() != 2 or b.dim() != 2 or b.shape[1] != a.shape[0]:
             raise LoaderError(f"LoRA shapes of {k}: down {tuple(a.shape)}, up {tuple(b.shape)}")
         if k in alpha:
@@ -241,7 +285,8 @@ def load_lora_adapter(unet: torch.nn.Module, path_or_dict, adapter_name: Optiona
         else:
             adapter_name = os.fspath(path_or_dict).rstrip("/").split("/")[-1].split(".")[0]
     lpb = getattr(getattr(unet, "config", None), "layers_per_block", 2)
-    adapter, skipped = parse_lora_state_dict(_read_tensors(path_or_dict), linear_module_paths(unet), adapter_name, lpb)
+    adapter, skipped = parse_lora_state_dict(_read_tensors(path_or_dict), linear_module_paths(unet), adapter_name, lpb,
+                                             conv_paths=conv_module_paths(unet))
     adapter.skipped_keys = skipped
     return adapter
 
@@ -265,6 +310,8 @@ def lora_state_dict(adapter: LoraAdapter, style: str = "peft") -> Dict[str, torc
                 out[f"{flat}.alpha"] = torch.tensor(float(a.shape[0]))
     for mod, (a, b) in adapter.weights.items():
         a, b = a.contiguous(), b.contiguous()
+        if a.dim() == 4:                      # a convolution target: files hold the up weight as a 1x1 conv
+            b = b.reshape(b.shape[0], b.shape[1], 1, 1)
         if style == "peft":
             out[f"unet.{mod}.lora_A.weight"], out[f"unet.{mod}.lora_B.weight"] = a, b
         elif style == "diffusers":

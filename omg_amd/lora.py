@@ -21,11 +21,14 @@ import torch
 
 from . import _lib as L
 from .attention import Attention
-from .modules import GEGLU, Linear
+from . import ops
+from .modules import Conv2d, GEGLU, Linear, bump_pointer_epoch, lora_conv_targets
 
 
 class LoraAdapter:
-    """One named adapter: ``weights[module_path] = (A [r, in], B [out, r])`` and its ``alpha``.
+    """One named adapter: ``weights[module_path] = (A [r, in], B [out, r])`` and its ``alpha``.  For a convolution target
+    (LoCon / PEFT ``Conv2d``) the pair is ``A [r, Cin, k, k]`` — a conv with the base layer's kernel, stride and padding — and
+    ``B [out, r]`` or ``[out, r, 1, 1]``.
 
     Layers may have different ranks (PEFT ``rank_pattern``, common in kohya files): ``rank`` is the largest one — the width a
     layer occupies in the slot stacks, smaller layers are zero-padded — and the PEFT factor ``alpha / r`` uses each layer's own
@@ -55,8 +58,14 @@ def lora_target_names(unet) -> List[str]:
     return out
 
 
-def make_synthetic_adapter(unet, name: str, rank: int, seed: int) -> LoraAdapter:
-    """Random adapter generated on the device: A ~ N(0, 1/in), B ~ N(0, 1e-2)."""
+def lora_conv_target_names(unet) -> List[str]:
+    """Every convolution a LoRA may target (:func:`omg_amd.modules.lora_conv_targets`)."""
+    return list(lora_conv_targets(unet))
+
+
+def make_synthetic_adapter(unet, name: str, rank: int, seed: int, conv: bool = False) -> LoraAdapter:
+    """Random adapter generated on the device: A ~ N(0, 1/in), B ~ N(0, 1e-2).  ``conv=True`` adds every convolution target,
+    drawn AFTER all Linear ones (the Linear weights of a seed do not depend on it)."""
     g = torch.Generator(device=unet.device).manual_seed(seed)
     w = {}
     for key in lora_target_names(unet):
@@ -64,6 +73,13 @@ def make_synthetic_adapter(unet, name: str, rank: int, seed: int) -> LoraAdapter
         a = torch.randn(rank, lin.in_features, generator=g, device=unet.device) * lin.in_features ** -0.5
         b = torch.randn(lin.out_features, rank, generator=g, device=unet.device) * 0.1
         w[key] = (a.to(unet.dtype), b.to(unet.dtype))
+    if conv:
+        for key in lora_conv_target_names(unet):
+            cv = unet.get_submodule(key)
+            fan_in = cv.cin * cv.ksize * cv.ksize
+            a = torch.randn(rank, cv.cin, cv.ksize, cv.ksize, generator=g, device=unet.device) * fan_in ** -0.5
+            b = torch.randn(cv.cout, rank, generator=g, device=unet.device) * 0.1
+            w[key] = (a.to(unet.dtype), b.to(unet.dtype))
     return LoraAdapter(name, w)
 
 
@@ -80,7 +96,8 @@ class LoraBank:
         return self.slots.index(tuple((n, float(w)) for n, w in combo))
 
     def build(self, slots: Sequence[Sequence[Tuple[str, float]]], scale: float = 1.0, mode: str = "merged") -> None:
-        """Materialise the slot stacks on every target Linear.  ``slots[s]`` = [(adapter name, weight), ...];
+        """Materialise the slot stacks on every target Linear and Conv2d (conv stacks in the packed ``[.., ky, kx, Cin]`` column order
+        of the conv weight, so that the merge ``W + s*B A`` is the same matrix product as for a Linear).  ``slots[s]`` = [(adapter name, weight), ...];
         ``scale`` is ``cross_attention_kwargs['scale']`` (0.8 in OMG, lora_pipeline.py:596) — a float, or one value per slot.
 
         mode="segment": keep A/B un-merged (PEFT's arithmetic: base(x) + s*B(A(x)), second K-segment of omg_gemm).
@@ -104,12 +121,21 @@ class LoraBank:
         r_tot = max(sum(self.adapters[n].rank for n, _ in s) for s in self.slots)
         r_tot = (r_tot + 7) // 8 * 8
         self.clear()
+        conv_ok = lora_conv_targets(self.unet)
         for key in sorted(keys):
-            lin = self.unet.get_submodule(key)
-            if not isinstance(lin, Linear):
-                raise L.OmgHipError(f"LoRA target {key} is not a Linear layer (conv LoRA is not supported)")
-            down = torch.zeros(len(self.slots), r_tot, lin.in_features, dtype=torch.float32, device=dev)
-            up = torch.zeros(len(self.slots), lin.out_features, r_tot, dtype=torch.float32, device=dev)
+            mod = self.unet.get_submodule(key)
+            is_conv = isinstance(mod, Conv2d)
+            if is_conv:
+                if key not in conv_ok:
+                    raise L.OmgHipError(f"LoRA target {key}: conv_in / conv_out, fp32-storage convolutions and convolutions whose input "
+                                        f"channels are no multiple of 64 are not LoRA targets")
+                n_in, n_out = mod.ksize * mod.ksize * mod.cin, mod.cout
+            elif isinstance(mod, Linear):
+                n_in, n_out = mod.in_features, mod.out_features
+            else:
+                raise L.OmgHipError(f"LoRA target {key} is neither a Linear nor a Conv2d layer")
+            down = torch.zeros(len(self.slots), r_tot, n_in, dtype=torch.float32, device=dev)
+            up = torch.zeros(len(self.slots), n_out, r_tot, dtype=torch.float32, device=dev)
             for s, combo in enumerate(self.slots):
                 r0 = 0
                 for name, w in combo:
@@ -118,15 +144,20 @@ class LoraBank:
                         r0 += ad.rank
                         continue
                     a, b = ad.weights[key]
+                    if is_conv:
+                        if a.dim() != 4 or tuple(a.shape[1:]) != (mod.cin, mod.ksize, mod.ksize) or b.reshape(b.shape[0], -1).shape != (mod.cout, a.shape[0]):
+                            raise L.OmgHipError(f"LoRA target {key}: down {tuple(a.shape)} / up {tuple(b.shape)} do not fit a "
+                                                f"{mod.ksize}x{mod.ksize} convolution {mod.cin} -> {mod.cout}")
+                        a, b = ops.pack_conv_weight(a), b.reshape(b.shape[0], -1)
                     r = a.shape[0]                                   # <= ad.rank; the rest of the adapter's band stays zero
                     down[s, r0:r0 + r] = a.to(dev).float()
                     up[s, :, r0:r0 + r] = b.to(dev).float() * (per_slot[s] * w * ad.scaling(key))
                     r0 += ad.rank
-            lin.lora_down = down.to(dt).contiguous()
-            lin.lora_up = up.to(dt).contiguous()
+            mod.lora_down = down.to(dt).contiguous()
+            mod.lora_up = up.to(dt).contiguous()
             if mode == "merged":
-                base = lin.weight.data.float()
-                lin.w_slots = torch.stack([base] + [base + up[s_] @ down[s_] for s_ in range(len(self.slots))]).to(dt).contiguous()
+                base = (ops.pack_conv_weight(mod.weight.data) if is_conv else mod.weight.data).float()
+                mod.w_slots = torch.stack([base] + [base + up[s_] @ down[s_] for s_ in range(len(self.slots))]).to(dt).contiguous()
         if mode == "merged":
             # the fused q|k|v (k|v) GEMM takes one weight stack per slot: an attention whose adapter targets only some of
             # its projections (custom PEFT target_modules) gets the base weight repeated for the others
@@ -141,8 +172,10 @@ class LoraBank:
         self._invalidate_packed()
 
     def _invalidate_packed(self) -> None:
-        """Only the modules whose packed images contain LoRA material (fused q|k|v stacks, GEGLU row-interleaved stacks):
-        conv weights are untouched by a slot change and keep their packed form (and their pointers)."""
+        """Only the modules whose packed images contain LoRA material (fused q|k|v stacks, GEGLU row-interleaved stacks).  The
+        convolutions' slot stacks (``Conv2d.lora_down`` / ``lora_up`` / ``w_slots``) are replaced by ``build`` / ``clear`` themselves
+        and are no part of ``Conv2d._packed``: the base convs' packed weights keep their form and their pointers.  Graphs that hold
+        pointers of the old stacks are dropped through ``version`` (engines) and the pointer epoch."""
         for m in self.unet.modules():
             if isinstance(m, (GEGLU, Attention)):
                 m.invalidate_packed()
@@ -150,7 +183,13 @@ class LoraBank:
                 m.invalidate_mx8_slots()
 
     def clear(self) -> None:
+        had_conv = False
         for m in self.unet.modules():
             if isinstance(m, Linear):
                 m.lora_down = m.lora_up = m.w_slots = None
+            elif isinstance(m, Conv2d):
+                had_conv |= m.has_lora_slots()
+                m.lora_down = m.lora_up = m.w_slots = None
+        if had_conv:      # captured graphs hold the freed conv stacks' pointers (and, in fp8 mode, took the other kernel)
+            bump_pointer_epoch()
         self._invalidate_packed()

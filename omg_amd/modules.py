@@ -219,6 +219,21 @@ class Conv2d(_Packed):
         self.weight = nn.Parameter(torch.empty(cout, cin, ksize, ksize, dtype=dtype, device=device), requires_grad=False)
         self.bias = nn.Parameter(torch.empty(cout, dtype=dtype, device=device), requires_grad=False)
         self.mx8 = False          # run on the block-scaled fp8 MFMA when fed an MX-fp8 feature map (UNet.set_conv_precision)
+        # LoRA bank (set by omg_amd.lora.LoraBank), all in the packed [.., ky, kx, Cin] column order of ``packed_weight``:
+        # [slots, r_pad, k*k*cin] (the k x k LoRA-down conv), [slots, cout, r_pad] (the 1x1 up conv, already scaled)
+        self.lora_down: Optional[torch.Tensor] = None
+        self.lora_up: Optional[torch.Tensor] = None
+        # merged mode: [1 + slots, cout, k*k*cin] = base weight followed by W + scale * B_s A_s per slot
+        self.w_slots: Optional[torch.Tensor] = None
+        self.lora_state: Optional[LoraState] = None   # set per forward by the UNet
+
+    def lora_eligible(self) -> bool:
+        """Whether the slot kernel (omg_conv2d_slots) can run this conv with a LoRA: 16-bit storage (not the fp32 VAE convs), input
+        channels in whole 64-wide K stages, Cout a multiple of 8.  The ONE rule behind :func:`lora_conv_targets`."""
+        return self.weight.dtype != torch.float32 and self.cin % 64 == 0 and self.cout % 8 == 0
+
+    def has_lora_slots(self) -> bool:
+        return self.w_slots is not None or self.lora_down is not None
 
     def packed_weight(self) -> torch.Tensor:
         if "w" not in self._packed:
@@ -234,8 +249,9 @@ class Conv2d(_Packed):
         return self._packed["wu"]
 
     def mx8_ok(self) -> bool:
-        """MX-fp8 eligibility: 3x3 / stride 1 on a 16-bit weight whose input channels are whole 32-element MX blocks."""
-        return self.mx8 and self.ksize == 3 and self.stride == 1 and self.cin % 32 == 0 and self.weight.dtype != torch.float32
+        """MX-fp8 eligibility: 3x3 / stride 1 on a 16-bit weight whose input channels are whole 32-element MX blocks.  A conv that
+        carries LoRA slots runs the 16-bit slot kernel (there is no MX-fp8 slot conv), so its GroupNorm writes a 16-bit map."""
+        return not self.has_lora_slots() and self.mx8 and self.ksize == 3 and self.stride == 1 and self.cin % 32 == 0 and self.weight.dtype != torch.float32
 
     def mx8_weight(self) -> "ops.Mx8Tensor":
         if "wq" not in self._packed:          # quantised once from the packed 16-bit weight; Cin padded with zeros to whole 128-wide K stages
@@ -259,8 +275,30 @@ class Conv2d(_Packed):
                 raise L.OmgHipError("the fp32 convolution supports stride 1 without concat / per-sample bias (all the VAE decoder needs)")
             return ops.conv2d_f32(x, self.packed_weight(), self.ksize, upsample=upsample, bias=self.bias, residual=residual,
                                   wu=self.wino_weight())
+        st = self.lora_state
+        if st is not None and self.has_lora_slots():
+            if x.shape[0] != st.groups:
+                raise L.OmgHipError("LoRA groups do not match the batch of the convolution")
+            if st.merged and self.w_slots is not None:      # one conv, a weight slot per sample
+                return ops.conv2d(x, self.w_slots, self.ksize, stride=self.stride, upsample=upsample, x2=x2, bias=self.bias,
+                                  group_bias=group_bias, residual=residual, w_group_adapter=st.group_adapter)
+            if not st.merged and self.lora_down is not None:
+                # PEFT's arithmetic: the k x k down conv (same taps, stride and upsample; samples without adapter skipped), then the
+                # base conv with the 1x1 up conv as second K-segment of the same accumulator
+                # `t` is torch.empty: the rows of a sample whose slot is -1 are never written (the down launch skips it) and never read
+                # (the segment of the base conv below is off for that sample)
+                t = ops.conv2d(x, self.lora_down, self.ksize, stride=self.stride, upsample=upsample, x2=x2, w_group_adapter=st.group_adapter)
+                return ops.conv2d(x, self.packed_weight(), self.ksize, stride=self.stride, upsample=upsample, x2=x2, bias=self.bias,
+                                  group_bias=group_bias, residual=residual, lora=ops.LoraSpec(t, self.lora_up, st.group_adapter))
         return ops.conv2d(x, self.packed_weight(), self.ksize, stride=self.stride, upsample=upsample, x2=x2, bias=self.bias,
                           group_bias=group_bias, residual=residual)
+
+
+def lora_conv_targets(net) -> dict:
+    """``{module path: Conv2d}`` of every convolution of ``net`` a LoRA may target: resnet conv1 / conv2 / conv_shortcut and the down- / up-sampling
+    convs.  ``conv_in`` / ``conv_out`` run on the NCHW boundary kernels and are never targets.  The loaders, the synthetic adapters and
+    ``LoraBank.build`` all ask this function."""
+    return {n: m for n, m in net.named_modules() if isinstance(m, Conv2d) and n not in ("conv_in", "conv_out") and m.lora_eligible()}
 
 
 class GroupNorm(nn.Module):

@@ -250,8 +250,17 @@ def gemm_mx8(a: Mx8Tensor, w: Mx8Tensor, *, out_dtype: torch.dtype = torch.float
 def conv2d(x1: torch.Tensor, w: torch.Tensor, ksize: int, *, stride: int = 1, upsample: bool = False,
            x2: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
            group_bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
-           out_scale: float = 1.0, act: int = L.ACT_NONE) -> torch.Tensor:
-    """NHWC implicit-GEMM conv; ``w`` is ``[Cout, ksize*ksize*(C1+C2)]`` (see pack_conv_weight)."""
+           out_scale: float = 1.0, act: int = L.ACT_NONE, w_group_adapter: Optional[torch.Tensor] = None,
+           lora: Optional[LoraSpec] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """NHWC implicit-GEMM conv; ``w`` is ``[Cout, ksize*ksize*(C1+C2)]`` (see pack_conv_weight).
+
+    LoRA on convolutions (``omg_conv2d_slots``): ``w`` may be 3-D ``[slots, Cout, K]`` together with ``w_group_adapter`` (int32
+    device tensor, one weight slot per sample; a sample with slot -1 is skipped and its rows of ``out`` stay as they are) — the
+    merged-weight conv and the LoRA-down conv; ``lora`` adds ``a2 @ w2[slot]^T`` (``a2``: the down conv's result, 2-D or NHWC)
+    into the accumulator of the samples whose slot is >= 0.  Without these arguments the call is ``omg_conv2d``, unchanged.
+    ``out`` (optional, NHWC contiguous): write there instead of allocating — what makes "skipped rows stay as they are" observable
+    (the canary test of the LoRA-down launch) and lets tools/conv_slots_bench.py time launches without the allocator.
+    """
     _dev(x1)
     B, Hin, Win, C1 = x1.shape
     assert x1.is_contiguous()
@@ -259,14 +268,20 @@ def conv2d(x1: torch.Tensor, w: torch.Tensor, ksize: int, *, stride: int = 1, up
     if x2 is not None:
         assert x2.is_contiguous() and x2.shape[:3] == x1.shape[:3]
         C2 = x2.shape[3]
-    Cout = w.shape[0]
-    assert w.is_contiguous() and w.shape[1] == ksize * ksize * (C1 + C2)
+    slots = w.dim() == 3 or w_group_adapter is not None or lora is not None
+    Cout = w.shape[-2]
+    assert w.is_contiguous() and w.shape[-1] == ksize * ksize * (C1 + C2)
     Hl, Wl = (2 * Hin, 2 * Win) if upsample else (Hin, Win)
     pad = 1 if ksize == 3 else 0
     Hout = (Hl + 2 * pad - ksize) // stride + 1
     Wout = (Wl + 2 * pad - ksize) // stride + 1
-    y = torch.empty((B, Hout, Wout, Cout), dtype=x1.dtype, device=x1.device)
-    a = L.Conv2dArgs()
+    if out is None:
+        y = torch.empty((B, Hout, Wout, Cout), dtype=x1.dtype, device=x1.device)
+    else:
+        y = out
+        assert y.is_contiguous() and tuple(y.shape) == (B, Hout, Wout, Cout) and y.dtype == x1.dtype
+    sa = L.Conv2dSlotsArgs() if slots else None
+    a = sa.conv if slots else L.Conv2dArgs()
     a.dtype = _dt(x1)
     a.B, a.Hin, a.Win, a.C1, a.C2 = B, Hin, Win, C1, C2
     a.Hout, a.Wout, a.Cout = Hout, Wout, Cout
@@ -280,12 +295,35 @@ def conv2d(x1: torch.Tensor, w: torch.Tensor, ksize: int, *, stride: int = 1, up
     a.out_scale = out_scale
     a.act = act
     a.Y = y.data_ptr()
+    k2 = 0
+    if slots:
+        adapter = w_group_adapter
+        sa.w_slot_stride = w.stride(0) if w.dim() == 3 else 0
+        if lora is not None:
+            a2, w2 = lora.a2, lora.w2
+            a2 = a2.reshape(-1, a2.shape[-1])
+            assert a2.stride(1) == 1 and a2.shape[0] == B * Hout * Wout and w2.stride(-1) == 1 and w2.shape[-2] == Cout and lora.a2_col_block == 0
+            k2 = w2.shape[-1]
+            sa.A2, sa.lda2, sa.W2, sa.K2 = a2.data_ptr(), a2.stride(0), w2.data_ptr(), k2
+            if w2.dim() == 3:
+                sa.ldw2, sa.w2_slot_stride = w2.stride(1), w2.stride(0)
+            else:
+                sa.ldw2, sa.w2_slot_stride = w2.stride(0), 0
+            if lora.group_adapter is not None:
+                adapter = lora.group_adapter
+        if adapter is not None:
+            assert adapter.dtype == torch.int32 and adapter.is_cuda and adapter.numel() == B
+        sa.group_adapter = _p(adapter)
+        fn, what, arg = L.lib().omg_conv2d_slots, "omg_conv2d_slots", sa
+    else:
+        fn, what, arg = L.lib().omg_conv2d, "omg_conv2d", a
     if _PROF is not None:
         t0 = _PROF.begin()
-        L.check(L.lib().omg_conv2d(C.byref(a), _stream()), "omg_conv2d")
-        _PROF.end("gemm", 2.0 * B * Hout * Wout * Cout * ksize * ksize * (C1 + C2), t0, ("conv", B * Hout * Wout, Cout, ksize * ksize * (C1 + C2), 0, 1, 0))
+        L.check(fn(C.byref(arg), _stream()), what)
+        K = ksize * ksize * (C1 + C2)
+        _PROF.end("gemm", 2.0 * B * Hout * Wout * Cout * (K + k2), t0, ("conv", B * Hout * Wout, Cout, K, k2, B if slots else 1, 0))
         return y
-    L.check(L.lib().omg_conv2d(C.byref(a), _stream()), "omg_conv2d")
+    L.check(fn(C.byref(arg), _stream()), what)
     return y
 
 

@@ -346,7 +346,7 @@ class UNet2DConditionModel(nn.Module):
         self.conv_norm_out = GroupNorm(cfg.norm_num_groups, c0, cfg.norm_eps, dtype, device)
         self.conv_out = Conv2d(c0, cfg.out_channels, 3, dtype=dtype, device=device)
         self._boundary = {}
-        self._linears: Optional[List[Linear]] = None
+        self._lora_modules: Optional[List[nn.Module]] = None      # Linear and Conv2d: everything that takes a LoraState
 
     # ------------------------------------------------------------------ diffusers-style attributes
     @property
@@ -464,9 +464,9 @@ class UNet2DConditionModel(nn.Module):
 
     # ------------------------------------------------------------------ LoRA selection
     def set_lora_state(self, state: Optional[LoraState]) -> None:
-        if self._linears is None:
-            self._linears = [m for m in self.modules() if isinstance(m, Linear)]
-        for m in self._linears:
+        if self._lora_modules is None:      # every LoRA target class: the Linear layers and the convolutions (conv LoRA, omg_conv2d_slots)
+            self._lora_modules = [m for m in self.modules() if isinstance(m, (Linear, Conv2d))]
+        for m in self._lora_modules:
             m.lora_state = state
 
     def refresh_cross_kv(self, ctx: torch.Tensor, state: Optional[LoraState]) -> None:
