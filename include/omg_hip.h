@@ -249,6 +249,18 @@ typedef struct {
 
 int omg_attn_fwd(const omg_attn_args* a, void* stream);
 
+/* omg_attn_fwd with a causal mask: key j is visible to query i iff j <= i and j < Nkv (top-left alignment; rows >= Nkv - 1 see
+ * every key, every row sees key 0).  Replaces the causal self-attention of transformers' CLIPTextModel (CLIPAttention with
+ * causal_attention_mask: bmm + additive -inf mask + softmax + bmm), which the reference reaches through encode_prompt for the global
+ * prompt, its negative and one prompt pair per concept (src/pipelines/lora_pipeline.py:315-347).  Same argument struct and the same
+ * meaning of qk_src, accumulate, out_scale and a strided O.  Served by the causal instance of the resident-K/V kernel only:
+ *   Nkv <= 128 (OMG_EINVAL above: the self-attention kernel has no causal form);
+ *   Vt from omg_transpose_v (mfma_key_order = 1, zero-padded columns) is required — row-major V alone is OMG_EINVAL;
+ *   O 16-byte aligned, ldo and o_bstride multiples of 8 elements.
+ * Scores and probabilities stay in fp32 and the mask is applied before the row maximum is taken, so a masked score of any size —
+ * or a non-finite one, as long as K and V hold no NaN / inf — leaves the visible keys' result untouched bit for bit. */
+int omg_attn_fwd_causal(const omg_attn_args* a, void* stream);
+
 /* V[B, Nkv, (head, 64)] (row stride ldv) -> Vt[B, heads, 64, Nkv_pad], zero padded.  mfma_key_order = 1 (what omg_attn_fwd
  * consumes): inside every group of 16 keys the order is [0-3, 8-11, 4-7, 12-15] — the operand order of the P·V MFMA, one
  * 16-byte LDS read per lane; 0: natural key order (a plain batched transpose, used by the VAE / text-encoder attention). */

@@ -131,6 +131,7 @@ SYMBOLS = {
     "omg_conv2d_f32_wino": (c_i32, [C.POINTER(Conv2dF32WinoArgs), c_vp]),
     "omg_cast_f32": (c_i32, [c_i32, c_vp, c_vp, c_i64, c_vp]),
     "omg_attn_fwd": (c_i32, [C.POINTER(AttnArgs), c_vp]),
+    "omg_attn_fwd_causal": (c_i32, [C.POINTER(AttnArgs), c_vp]),
     "omg_transpose_v": (c_i32, [c_i32, c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp]),
     "omg_groupnorm_ws_floats": (c_i64, [c_i32, c_i32, c_i32]),
     "omg_groupnorm": (c_i32, [c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),

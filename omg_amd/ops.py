@@ -521,11 +521,14 @@ def _attn_args(q, k, vt, heads, nkv, scale, qk_src, out, accumulate, out_scale) 
 
 def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, scale: float, *,
               qk_src: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-              accumulate: bool = False, out_scale: float = 1.0) -> torch.Tensor:
+              accumulate: bool = False, out_scale: float = 1.0, causal: bool = False) -> torch.Tensor:
     """Fused attention.  q: (B,Nq,>=heads*64) view, k: (B,Nkv,>=heads*64) view, vt from :func:`value_operand` (or transpose_v).
 
     ``qk_src`` (int32 device tensor [B]) implements the controller's probability replacement:
     sample b uses Q,K of sample qk_src[b] and its own V.
+
+    ``causal``: query i sees keys j <= i only (top-left alignment; `omg_attn_fwd_causal`: at most 128 keys, ``vt`` from
+    :func:`transpose_v` in its default key order; anything else is an error, not another path).
     """
     _dev(q)
     assert q.stride(2) == 1 and k.stride(2) == 1
@@ -533,12 +536,13 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, sc
     if out is None:
         out = torch.empty((B, Nq, heads * 64), dtype=q.dtype, device=q.device)
     a = _attn_args(q, k, vt, heads, k.shape[1], scale, qk_src, out, accumulate, out_scale)
+    fn, what = (L.lib().omg_attn_fwd_causal, "omg_attn_fwd_causal") if causal else (L.lib().omg_attn_fwd, "omg_attn_fwd")
     if _PROF is not None:
         t0 = _PROF.begin()
-        L.check(L.lib().omg_attn_fwd(C.byref(a), _stream()), "omg_attn_fwd")
+        L.check(fn(C.byref(a), _stream()), what)
         _PROF.end("attn", 4.0 * B * heads * Nq * k.shape[1] * 64, t0, ("attn", B, heads, Nq, k.shape[1]))
         return out
-    L.check(L.lib().omg_attn_fwd(C.byref(a), _stream()), "omg_attn_fwd")
+    L.check(fn(C.byref(a), _stream()), what)
     return out
 
 

@@ -1,20 +1,23 @@
 """CLIP text transformers of SDXL's ``encode_prompt`` on the HIP kernels — row N4 of SURVEY.md §8f (the reference reaches them
-through ``self.encode_prompt`` / ``concept_models.encode_prompt``, /root/reference src/pipelines/lora_pipeline.py:315-347).
+through ``self.encode_prompt`` / ``concept_models.encode_prompt``, src/pipelines/lora_pipeline.py:315-347: the global prompt, its
+negative and one prompt pair per concept, inside every ``__call__``).
 
 State-dict keys equal transformers' ``CLIPTextModel`` / ``CLIPTextModelWithProjection`` (``text_model.embeddings.*``,
 ``text_model.encoder.layers.i.{self_attn.{q,k,v,out}_proj, layer_norm1, layer_norm2, mlp.fc1, mlp.fc2}``,
 ``text_model.final_layer_norm``, ``text_projection.weight``), so ``omg_amd.loaders.load_model_weights`` fills it from
 ``text_encoder/model.safetensors``.  Tokenisation stays with the caller (no tokenizer files exist offline).
 
-This path runs once per prompt (77 tokens), so it is composed from kernels the UNet and VAE already validated rather than
-given kernels of its own:
+Per layer, whatever the number of prompts and heads:
   * LayerNorm, q|k|v / out_proj / fc1 / fc2 as `omg_gemm` with bias and residual epilogues;
-  * causal attention per (sample, head) = scores GEMM (out_scale 1/sqrt(64)) + additive mask (`omg_add_inplace`) +
-    `omg_softmax_rows` + P·V GEMM — the flash kernel has no causal mask yet;
+  * causal attention = one `omg_transpose_v` of the V columns (MFMA key order) + ONE `omg_attn_fwd_causal` launch over all samples
+    and heads: Q and K are strided views of the fused q|k|v projection, the output goes straight into the (B·T, d) buffer
+    out_proj reads; scores and probabilities stay in fp32 inside the kernel (the flash kernel the UNet's cross-attention runs,
+    with the causal mask: key j visible to query i iff j <= i);
   * quick_gelu(x) = silu(1.702 x) / 1.702: fc1 with ``out_scale`` 1.702, `omg_silu`, and fc2's weights divided by 1.702;
   * exact gelu (OpenCLIP-bigG): fc1 run as a GEGLU GEMM whose value half is the constant 1 (zero weights, bias 1).
-Sequences are padded from 77 to 80 positions (GEMM extents are multiples of 8); the causal mask keeps the padding out of
-every real position.  The embedding lookup is a torch gather (data movement, no arithmetic).
+Sequences are padded from 77 to 80 positions (GEMM extents are multiples of 8) with the end-of-text token; the causal mask keeps
+the padding out of every real position, and the padded rows themselves attend like any other row, so they stay finite for the
+GEMMs and LayerNorms that read them.  The embedding lookup is a torch gather (data movement, no arithmetic).
 """
 from __future__ import annotations
 
@@ -124,7 +127,7 @@ class ClipTextEncoder(nn.Module):
 
     def _pack(self):
         """Derived weight images: q|k|v rows concatenated; quick_gelu's 1/1.702 folded into fc2; gelu's fc1 as a GEGLU GEMM with
-        a constant-one value half; the causal mask; active LoRA deltas merged."""
+        a constant-one value half; active LoRA deltas merged."""
         cfg, dev, dt = self.config, self.device, self._dtype
         layers = []
         for li, lyr in enumerate(self.text_model.encoder.layers):
@@ -146,11 +149,9 @@ class ClipTextEncoder(nn.Module):
                 pk["w2"] = w2
             layers.append(pk)
         T = self.TP
-        mask = torch.zeros(T, T, dtype=dt, device=dev)
-        mask.masked_fill_(torch.ones(T, T, dtype=torch.bool, device=dev).triu(1), -30000.0)
         pos = torch.zeros(T, cfg.hidden_size, dtype=dt, device=dev)
         pos[: cfg.max_position_embeddings] = self.text_model.embeddings.position_embedding.weight.data
-        self._packed = {"layers": layers, "mask": mask, "pos": pos}
+        self._packed = {"layers": layers, "pos": pos}
 
     @torch.no_grad()
     def forward(self, input_ids: torch.Tensor, clip_skip: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -170,7 +171,6 @@ class ClipTextEncoder(nn.Module):
         ids = torch.full((B, T), cfg.eos_token_id, dtype=torch.long, device=input_ids.device)
         ids[:, :T0] = input_ids
         x = (self.text_model.embeddings.token_embedding.weight.data[ids] + pk["pos"]).reshape(B * T, d).contiguous()
-        scores = torch.empty(T, T, dtype=x.dtype, device=x.device)
         penultimate = x
         n_layers = len(self.text_model.encoder.layers)
         skip = int(clip_skip or 0)
@@ -181,14 +181,9 @@ class ClipTextEncoder(nn.Module):
                 penultimate = x                                     # hidden_states[-(2 + skip)] = the input of layer n - 1 - skip
             h = lyr.layer_norm1(x)
             qkv = ops.gemm(h, w["wqkv"], bias=w["bqkv"]).view(B, T, 3 * d)
-            vt = ops.transpose_v(qkv[:, :, 2 * d:], heads, mfma_order=False)   # (B, heads, 64, 128), plain transpose
+            vt = ops.transpose_v(qkv[:, :, 2 * d:], heads)                     # (B, heads, 64, 128), MFMA key order, keys >= 80 zero
             attn = torch.empty(B * T, d, dtype=x.dtype, device=x.device)
-            for b in range(B):
-                for hh in range(heads):
-                    ops.gemm(qkv[b, :, hh * 64:(hh + 1) * 64], qkv[b, :, d + hh * 64: d + (hh + 1) * 64], out=scores, out_scale=0.125)
-                    ops.add_(scores, pk["mask"])
-                    ops.softmax_rows_(scores, 1.0)
-                    ops.gemm(scores, vt[b, hh, :, :T], out=attn[b * T:(b + 1) * T, hh * 64:(hh + 1) * 64])
+            ops.attention(qkv[:, :, :d], qkv[:, :, d:2 * d], vt, heads, 0.125, out=attn.view(B, T, d), causal=True)
             x = ops.gemm(attn, w["wo"], bias=lyr.self_attn.out_proj.bias.data, residual=x)
             h = lyr.layer_norm2(x)
             if cfg.hidden_act == "quick_gelu":
