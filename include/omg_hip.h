@@ -267,6 +267,37 @@ int omg_attn_fwd_causal(const omg_attn_args* a, void* stream);
 int omg_transpose_v(int dtype, const void* V, int64_t ldv, int64_t v_bstride,
                     int B, int heads, int Nkv, int Nkv_pad, void* Vt, int mfma_key_order, void* stream);
 
+/* omg_transpose_v_mapped — the general prompt-to-prompt cross-attention edit, folded into V.
+ *
+ * Replaces AttentionReplace.replace_cross_attention and the alpha blend of AttentionControlEdit.forward
+ * (src/prompt_attention/p2p_attention.py:131-133, :146-147: einsum('hpw,bwn->bhpn', base, mapper) * alpha + (1 - alpha) * own) for a
+ * non-identity mapper (word swap) and for cross-replace windows, without the probability tensor: with P_b / P_e the base / edited
+ * sample's probabilities,
+ *     (P_b M_e * alpha_e + (1 - alpha_e) * P_e) V_e  =  P_b V'_e + P_e V''_e,
+ *     V'_e[w, :] = sum_n M_e[w, n] alpha_e[n] V_e[n, :],    V''_e[n, :] = (1 - alpha_e[n]) V_e[n, :].
+ * The caller runs omg_attn_fwd twice: qk_src = base on Vt_mapped, then the sample's own Q, K with accumulate = 1 on Vt_own.
+ *
+ * One launch for the whole batch.  Both outputs are [B, heads, 64, Nkv_pad] in omg_transpose_v's mfma_key_order = 1 layout, columns
+ * >= Nkv written as zeros.  Row b with edit_of[b] < 0: Vt_mapped is the plain transpose (bit-equal to omg_transpose_v), Vt_own is
+ * zero.  Other rows use tables edit_of[b] (clamped to E - 1) at step *step_idx (clamped to [0, steps - 1]; NULL = row 0): the step is
+ * read on the device, so one captured graph serves every step.  fp32 accumulation over n, one rounding to dtype; a term whose
+ * coefficient is exactly 0 is skipped, so inf / NaN in a V row that no coefficient selects does not reach the output.
+ * OMG_EINVAL (nothing written): Nkv > 128, Nkv_pad % 64 != 0 or < Nkv, E <= 0, steps <= 0, ld_mapper < Nkv, V not 16-byte aligned
+ * or ldv / v_bstride not multiples of 8 elements, outputs not 16-byte aligned, a NULL operand. */
+typedef struct {
+  int32_t dtype;                  /* OMG_F16 / OMG_BF16                                                        */
+  int32_t B, heads, Nkv, Nkv_pad; /* head_dim is 64; Nkv <= 128; Nkv_pad % 64 == 0                             */
+  const void* V; int64_t ldv; int64_t v_bstride;   /* [B, Nkv, (head, 64)] as omg_gemm wrote the [k|v] projection (elements) */
+  const int32_t* edit_of;         /* device [B]: index into the tables, or -1 for a row that is not edited     */
+  int32_t E, steps;
+  const float* mapper; int64_t ld_mapper; int64_t mapper_estride;        /* M_e[w][n] = mapper[e * estride + w * ld + n]  */
+  const float* alpha; int64_t alpha_step_stride; int64_t alpha_estride;  /* alpha[step * step_stride + e * estride + n]   */
+  const int32_t* step_idx;        /* device scalar, or NULL                                                     */
+  void* Vt_mapped; void* Vt_own;
+} omg_vmap_args;
+
+int omg_transpose_v_mapped(const omg_vmap_args* a, void* stream);
+
 /* ------------------------------------------------------------------------
  * Normalisation.  GroupNorm (NHWC, fp32 statistics as sums shifted by a
  * per-channel pivot and merged as (mean, M2), so that |mean| >> std does not

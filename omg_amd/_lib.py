@@ -105,6 +105,17 @@ class AttnArgs(C.Structure):
     ]
 
 
+class VMapArgs(C.Structure):
+    _fields_ = [
+        ("dtype", c_i32), ("B", c_i32), ("heads", c_i32), ("Nkv", c_i32), ("Nkv_pad", c_i32),
+        ("V", c_vp), ("ldv", c_i64), ("v_bstride", c_i64),
+        ("edit_of", c_vp), ("E", c_i32), ("steps", c_i32),
+        ("mapper", c_vp), ("ld_mapper", c_i64), ("mapper_estride", c_i64),
+        ("alpha", c_vp), ("alpha_step_stride", c_i64), ("alpha_estride", c_i64),
+        ("step_idx", c_vp), ("Vt_mapped", c_vp), ("Vt_own", c_vp),
+    ]
+
+
 class StepArgs(C.Structure):
     _fields_ = [
         ("C", c_i32), ("H", c_i32), ("W", c_i32), ("Hm", c_i32), ("Wm", c_i32),
@@ -133,6 +144,7 @@ SYMBOLS = {
     "omg_attn_fwd": (c_i32, [C.POINTER(AttnArgs), c_vp]),
     "omg_attn_fwd_causal": (c_i32, [C.POINTER(AttnArgs), c_vp]),
     "omg_transpose_v": (c_i32, [c_i32, c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp]),
+    "omg_transpose_v_mapped": (c_i32, [C.POINTER(VMapArgs), c_vp]),
     "omg_groupnorm_ws_floats": (c_i64, [c_i32, c_i32, c_i32]),
     "omg_groupnorm": (c_i32, [c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "omg_layernorm": (c_i32, [c_i32, c_vp, c_i64, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp, c_i64, c_vp]),

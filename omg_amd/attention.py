@@ -14,8 +14,11 @@ Three processors are provided:
   With an OMG ``AttentionReplace`` controller whose mapper is the identity and alpha is 1 (always,
   in OMG's flows) the controller's in-place edit ``probs[cond_i] := probs[cond_0]`` is executed as
   *probability borrowing* inside the flash-attention kernel (never materialising the
-  ``(B*heads, N, N)`` tensor).  For any other controller it falls back to the reference's literal
-  sequence (scores -> softmax -> controller(probs) -> bmm) on HIP kernels ("protocol mode").
+  ``(B*heads, N, N)`` tensor).  A word swap (non-identity mapper) or a cross-replace window (alpha < 1)
+  folds into V: two launches of the same kernel on the images of ``omg_transpose_v_mapped``.  Only a
+  controller without ``fused_edit``, one with ``local_blend``, or ``force_protocol = True`` runs the
+  reference's literal sequence (scores -> softmax -> controller(probs) -> bmm) on HIP kernels
+  ("protocol mode").
 * :class:`IPAttnProcessor2_0` — text + scale * image-prompt attention of the InstantID concept
   UNet (src/ip_adapter/attention_processor.py:296-424).
 """
@@ -176,11 +179,15 @@ class Attention(nn.Module):
             q, k, v = qkv[:, :, :inner], qkv[:, :, inner:2 * inner], qkv[:, :, 2 * inner:]
         return q, k, ops.value_operand(v, self.heads)
 
-    def project_cross(self, ctx: torch.Tensor):
+    def project_cross(self, ctx: torch.Tensor, with_v: bool = False):
         """ctx (B,Nk,Cx) -> K view and V^T of a constant ``encoder_hidden_states``.
 
         Cached per (ctx shape, LoRA state): a hit returns the stored projections; a miss for a shape seen before
-        recomputes INTO the stored tensors (pointers stay valid for captured hipGraphs); entries keep ``ctx`` alive."""
+        recomputes INTO the stored tensors (pointers stay valid for captured hipGraphs); entries keep ``ctx`` alive.
+
+        ``with_v``: also return the row-major V (the V columns of the fused [k|v] buffer, or ``to_v(ctx)`` under segment-mode LoRA) and
+        the entry's two-slot list of mapped V^T images (omg_transpose_v_mapped writes them every step; allocated by the first caller and
+        kept with the entry, so that their pointers survive across steps as K / V^T do)."""
         st = self.to_k.lora_state
         skey = (tuple(ctx.shape), None if st is None else (st.group_adapter.data_ptr(), st.merged))
         stamp = (ctx.data_ptr(), ctx._version)
@@ -188,7 +195,7 @@ class Attention(nn.Module):
         if hit is not None:
             self._kv_cache[skey] = self._kv_cache.pop(skey)      # most recently USED last: eviction takes the idle shape, not the oldest-inserted one
         if hit is not None and hit[0] == stamp:
-            return hit[1], hit[2]
+            return (hit[1], hit[2], hit[5], hit[6]) if with_v else (hit[1], hit[2])
         B, Nk, Cx = ctx.shape
         inner = self.inner_dim
         kv_out = hit[4] if hit is not None else None
@@ -210,8 +217,9 @@ class Attention(nn.Module):
         if hit is None and len(self._kv_cache) >= 4:
             self._kv_cache.pop(next(iter(self._kv_cache)))
             bump_pointer_epoch()                      # a captured graph may still point at the evicted K / V^T
-        self._kv_cache[skey] = (stamp, k, vt, ctx, kv_out)
-        return k, vt
+        images = hit[6] if hit is not None else [None, None]
+        self._kv_cache[skey] = (stamp, k, vt, ctx, kv_out, v, images)
+        return (k, vt, v, images) if with_v else (k, vt)
 
 
 def _ip_kv(attn: Attention, ip_ctx: torch.Tensor):
@@ -303,6 +311,8 @@ class FusedAttnProcessor:
 class RegionControlNet_AttnProcessor(FusedAttnProcessor):
     """Drop-in for the reference class of the same name (lora_pipeline.py:61-133)."""
 
+    force_protocol = False      # True: the reference's literal sequence on materialised probabilities for every controller (comparison arm)
+
     def __init__(self, attention_op=None, controller=None, place_in_unet=None):
         self.attention_op = attention_op
         self.controller = controller
@@ -310,6 +320,48 @@ class RegionControlNet_AttnProcessor(FusedAttnProcessor):
 
     def _fusable(self) -> bool:
         return self.controller is None or getattr(self.controller, "is_pure_replacement", False)
+
+    def _general(self) -> bool:
+        """A controller whose edit folds into V (``fused_edit``: any mapper, any alpha); ``local_blend`` edits latents and stays outside."""
+        c = self.controller
+        return hasattr(c, "fused_edit") and hasattr(c, "edit_tables") and getattr(c, "local_blend", None) is None
+
+    def _general_call(self, attn: Attention, hidden_states, encoder_hidden_states, residual, kw):
+        """Word swap / cross-replace windows on the flash kernel.  Self-attention and the "borrow" / "own" cross steps are one launch
+        (qk_src or none); a "mixed" cross step is O = P_base V' + P_own V'': one omg_transpose_v_mapped over the batch, omg_attn_fwd with
+        qk_src on V', a second omg_attn_fwd accumulating on V'' (zero for the rows that are not edited)."""
+        ctl = self.controller
+        x = _to_tokens(attn, hidden_states)
+        B, N, _ = x.shape
+        is_cross = encoder_hidden_states is not None
+        main_b = kw.pop("omg_main_batch", None)
+        n_img = kw.pop("omg_images", 1)
+        if kw.pop("omg_twin", False):
+            raise L.OmgHipError("omg_twin (dedup) needs a pure-replacement controller")
+        ip_ctx = kw.pop("omg_ip_tokens", None)
+        ip_row0 = kw.pop("omg_ip_rows", 0)
+        v = images = None
+        if is_cross:
+            q = attn.to_q(x)
+            if ctl.cross_kind() == "mixed":
+                k, vt, v, images = attn.project_cross(encoder_hidden_states, with_v=True)
+            else:
+                k, vt = attn.project_cross(encoder_hidden_states)
+        else:
+            q, k, vt = attn.project_self(x)
+        kind, src, edit_of = ctl.fused_edit(is_cross, N, main_b or B, self.place_in_unet, device=x.device, total_batch=B, images=n_img)
+        if kind == "mixed":
+            mapper, alpha, step = ctl.edit_tables(x.device)
+            if images[0] is None:
+                images[0], images[1] = torch.empty_like(vt), torch.empty_like(vt)
+            vm, vo = ops.transpose_v_mapped(v, attn.heads, edit_of, mapper, alpha, step, nkv_pad=vt.shape[3], out=(images[0], images[1]))
+            o = ops.attention(q, k, vm, attn.heads, attn.scale, qk_src=src)
+            ops.attention(q, k, vo, attn.heads, attn.scale, out=o, accumulate=True)
+        else:
+            o = ops.attention(q, k, vt, attn.heads, attn.scale, qk_src=src)
+        if is_cross and ip_ctx is not None and attn.ip_kv_weight is not None:
+            _ip_branch(attn, q, o, ip_ctx, ip_row0)
+        return attn.to_out[0](o, residual=residual)
 
     def _qk_src(self, attn, is_cross, n_tokens, batch, device, main_batch=None, images=1):
         if self.controller is None:
@@ -324,10 +376,16 @@ class RegionControlNet_AttnProcessor(FusedAttnProcessor):
 
     def __call__(self, attn: Attention, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
                  scale: float = 1.0, residual: Optional[torch.Tensor] = None, **cross_attention_kwargs):
-        if self._fusable() or cross_attention_kwargs.get("omg_bypass_controller", False):
+        bypass = cross_attention_kwargs.get("omg_bypass_controller", False)
+        if bypass or self.controller is None or (self._fusable() and not self.force_protocol):
             return super().__call__(attn, hidden_states, encoder_hidden_states, attention_mask, temb, scale,
                                     residual=residual, **cross_attention_kwargs)
-        # ---- protocol mode: the reference's literal sequence (lora_pipeline.py:98-124)
+        if self._general() and not self.force_protocol:
+            if attention_mask is not None:
+                raise L.OmgHipError("attention_mask is not supported")
+            return self._general_call(attn, hidden_states, encoder_hidden_states, residual, cross_attention_kwargs)
+        # ---- protocol mode: the reference's literal sequence (lora_pipeline.py:98-124) — controllers that only have __call__, local_blend,
+        # or force_protocol
         if cross_attention_kwargs.get("omg_images", 1) != 1:
             raise L.OmgHipError("protocol mode (non-identity mapper) runs one request at a time")
         x = _to_tokens(attn, hidden_states)

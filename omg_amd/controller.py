@@ -13,6 +13,11 @@ On top of that protocol the controller exposes what the fused kernel needs:
   ``__call__`` and returns the per-sample "borrow Q,K from" index vector (device int32) for
   ``omg_attn_fwd``, or None when this call leaves the probabilities untouched.
 
+* ``cross_kind()`` / ``fused_edit(...)`` / ``edit_tables(device)`` — the same for ANY mapper and alpha (word swap, cross-replace
+  windows; p2p_attention.py:131-133, :147): the host classifies the step ("borrow" / "own" / "mixed"), a "mixed" cross layer runs
+  ``O_e = P_base V' + P_own V''`` on the two images ``omg_transpose_v_mapped`` builds from fp32 copies of the mapper and of the alpha table;
+  the alpha row is selected on the device through a step counter (``bind_step_counter``), so captured graphs follow the step.
+
 The counters live on the host (they select which pre-built index tensor / captured graph is used);
 nothing here synchronises with the device.
 """
@@ -162,11 +167,22 @@ class AttentionReplace:
         self.batch_size = len(prompts)
         self.local_blend = local_blend
         self.device, self.dtype = device, dtype
-        self.cross_replace_alpha = get_time_words_attention_alpha(prompts, num_steps, cross_replace_steps, tokenizer).to(device)
+        alpha = get_time_words_attention_alpha(prompts, num_steps, cross_replace_steps, tokenizer)
+        self.cross_replace_alpha = alpha.to(device)
         if isinstance(self_replace_steps, float):
             self_replace_steps = (0, self_replace_steps)
         self.num_self_replace = (int(num_steps * self_replace_steps[0]), int(num_steps * self_replace_steps[1]))
-        self.mapper = get_replacement_mapper(prompts, tokenizer).to(dtype=dtype, device=device)
+        mapper = get_replacement_mapper(prompts, tokenizer)
+        # fp32 tables of the fused general edit (omg_transpose_v_mapped), taken BEFORE the mapper is rounded to `dtype` below; the host copies
+        # classify a step without touching the device
+        self._alpha_host = alpha.reshape(alpha.shape[0], alpha.shape[1], MAX_NUM_WORDS).float().contiguous()
+        self._mapper_host = mapper.float().contiguous()
+        self._tables: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
+        self._edit_cache: Dict[Tuple, torch.Tensor] = {}
+        self._step_dev: Dict[str, torch.Tensor] = {}        # the controller's own device copy of cur_step, per device
+        self._step_dev_val: Dict[str, int] = {}
+        self._bound_step: Optional[Tuple[torch.Tensor, int]] = None
+        self.mapper = mapper.to(dtype=dtype, device=device)
         self.num_att_layers = -1
         self.cur_step = 0
         self.cur_att_layer = 0
@@ -174,6 +190,9 @@ class AttentionReplace:
         self._identity_mapper = all(torch.equal(m.float().cpu(), eye) for m in self.mapper)
         self.is_pure_replacement = bool(local_blend is None and self._identity_mapper and bool((self.cross_replace_alpha == 1).all()))
         self._src_cache: Dict[Tuple, torch.Tensor] = {}
+        ident = bool(all(torch.equal(m, eye) for m in self._mapper_host))
+        self._cross_kinds = ["borrow" if ident and bool((a == 1).all()) else "own" if bool((a == 0).all()) else "mixed"
+                             for a in self._alpha_host]
 
     # ------------------------------------------------------------------ protocol (B2)
     @property
@@ -250,6 +269,84 @@ class AttentionReplace:
             t = torch.tensor(v, dtype=torch.int32, device=device)
             self._src_cache[key] = t
         return t
+
+    # ---- the general cross edit (word swap, cross-replace windows) folded into V
+    def cross_kind(self, step: Optional[int] = None) -> str:
+        """What the cross-attention edit of step ``step`` (default: ``cur_step``) amounts to — host-side, no sync:
+        "borrow": M = I and alpha == 1 for every edit: probs[edit] := probs[base], the flash kernel's qk_src alone;
+        "own"   : alpha == 0 for every edit: the probabilities stay the sample's own, a plain attention;
+        "mixed" : anything else: O_e = P_b V' + P_e V'' on the two images of omg_transpose_v_mapped."""
+        step = self.cur_step if step is None else step
+        return self._cross_kinds[min(max(step, 0), len(self._cross_kinds) - 1)]      # clamped like the kernel's own table index
+
+    def edit_of_vector(self, batch: int, device, total_batch: Optional[int] = None, images: int = 1) -> torch.Tensor:
+        """Per request [-1 .. -1 | -1, 0, 1, ...]: conditional sample i >= 1 is edit i - 1 of the tables; every other row is plain."""
+        total = total_batch or batch * images
+        key = (batch, total, images, str(device))
+        t = self._edit_cache.get(key)
+        if t is None:
+            n = batch // 2
+            t = torch.tensor(([-1] * (n + 1) + list(range(batch - n - 1))) * images + [-1] * (total - batch * images),
+                             dtype=torch.int32, device=device)
+            self._edit_cache[key] = t
+        return t
+
+    def bind_step_counter(self, step_idx: Optional[torch.Tensor], offset: int = 0) -> None:
+        """``step_idx`` (device int32 scalar) + ``offset`` equals ``cur_step`` at every step from now on — a denoising loop that advances
+        its counter on the device (and replays captured graphs) binds it here; None gives the counter back to the controller."""
+        self._bound_step = None if step_idx is None else (step_idx, int(offset))
+
+    def _own_step_counter(self, device, refresh: bool = True) -> torch.Tensor:
+        key = str(device)
+        t = self._step_dev.get(key)
+        if t is None:
+            t = self._step_dev[key] = torch.zeros(1, dtype=torch.int32, device=device)
+            self._step_dev_val[key] = 0
+        if refresh and self._step_dev_val[key] != self.cur_step:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("a captured step needs a device step counter: bind_step_counter(step_idx) before capturing")
+            t.fill_(self.cur_step)
+            self._step_dev_val[key] = self.cur_step
+        return t
+
+    def edit_tables(self, device=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(mapper fp32 (E, 77, 77), alpha fp32 (rows, E, 77), step) on ``device``, for the layer ``fused_edit`` was last asked about:
+        its edit is row ``step[0]`` of ``alpha`` — read on the device, so that a captured graph follows the counter instead of replaying the step it was recorded at."""
+        device = torch.device(device or self.device or "cuda")
+        key = str(device)
+        tabs = self._tables.get(key)
+        if tabs is None:
+            tabs = self._tables[key] = (self._mapper_host.to(device), self._alpha_host.to(device))
+        mapper, alpha = tabs
+        if self._bound_step is not None:
+            step, off = self._bound_step
+            if not 0 <= off < alpha.shape[0]:
+                raise RuntimeError(f"step counter offset {off} outside the {alpha.shape[0]}-row alpha table")
+            return mapper, alpha[off:], step
+        # not refreshed here: fused_edit wrote the step of the layer being run before it ticked
+        return mapper, alpha, self._own_step_counter(device, refresh=False)
+
+    def fused_edit(self, is_cross: bool, n_tokens: int, batch: int, place_in_unet: str = "", device=None,
+                   total_batch: Optional[int] = None, images: int = 1):
+        """``fused_qk_src`` for ANY mapper / alpha: advances the counters exactly like ``__call__`` and returns (kind, qk_src, edit_of):
+        "own" -> (None, None): a plain attention; "borrow" -> (qk_src, None): today's probability borrowing; "mixed" (cross layers
+        only) -> (qk_src, edit_of): attention with qk_src on V', then the rows' own Q, K accumulating on V'' (``edit_tables``)."""
+        if self.local_blend is not None:
+            raise RuntimeError("fused_edit does not cover local_blend")
+        n2 = 2 * self.batch_size
+        if batch != n2 and not (batch == n2 - 1 and self.is_pure_replacement):
+            raise ValueError(f"controller built for {self.batch_size} prompts expects a batch of {n2} ([unc..., cond...]), got {batch}")
+        dev = device or self.device or "cuda"
+        kind = self.cross_kind() if is_cross else ("borrow" if self.replaces(False, n_tokens) else "own")
+        src = edit_of = None
+        if kind != "own":
+            src = self.qk_src_vector(batch, dev, total_batch, images)
+        if kind == "mixed":
+            edit_of = self.edit_of_vector(batch, dev, total_batch, images)
+            if self._bound_step is None:
+                self._own_step_counter(torch.device(dev))      # bring the device copy up to cur_step BEFORE the tick below may advance it
+        self._tick()
+        return kind, src, edit_of
 
     def skip_layer(self) -> None:
         """One attention call whose conditional samples are all identical to the base sample (the caller has proven it): a pure

@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional, Sequence
+from typing import Optional, Sequence, Tuple
 
 import torch
 
@@ -480,6 +480,46 @@ def transpose_v(v: torch.Tensor, heads: int, nkv_pad: Optional[int] = None, out:
     L.check(L.lib().omg_transpose_v(_dt(v), v.data_ptr(), v.stride(1), v.stride(0), B, heads, Nkv, nkv_pad,
                                     vt.data_ptr(), int(mfma_order), _stream()), "omg_transpose_v")
     return vt
+
+
+def transpose_v_mapped(v: torch.Tensor, heads: int, edit_of: torch.Tensor, mapper: torch.Tensor, alpha: torch.Tensor,
+                       step_idx: Optional[torch.Tensor] = None, nkv_pad: Optional[int] = None,
+                       out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The two V^T images of a general prompt-to-prompt cross edit (omg_transpose_v_mapped), one launch for the batch.
+
+    ``v``: (B, Nkv <= 128, >= heads*64) view with unit inner stride; ``edit_of``: int32 (B,) table index per row, -1 = not edited;
+    ``mapper``: fp32 (E, >= Nkv, >= Nkv); ``alpha``: fp32 (steps, E, >= Nkv); ``step_idx``: device int32 scalar selecting the alpha row
+    (None = row 0).  Returns (Vt_mapped, Vt_own), each (B, heads, 64, nkv_pad) in :func:`transpose_v`'s MFMA key order; pass ``out`` to
+    write into existing buffers (pointer-stable across steps for captured graphs)."""
+    _dev(v)
+    B, Nkv = v.shape[0], v.shape[1]
+    if nkv_pad is None:
+        nkv_pad = (Nkv + 63) // 64 * 64
+    assert v.stride(2) == 1
+    assert edit_of.dtype == torch.int32 and edit_of.is_contiguous() and edit_of.numel() == B and edit_of.device == v.device
+    assert mapper.dtype == torch.float32 and mapper.dim() == 3 and mapper.stride(2) == 1 and mapper.device == v.device
+    assert alpha.dtype == torch.float32 and alpha.dim() == 3 and alpha.stride(2) == 1 and alpha.device == v.device
+    assert alpha.shape[1] == mapper.shape[0]
+    if mapper.shape[1] < Nkv or alpha.shape[2] < Nkv:
+        raise L.OmgHipError(f"transpose_v_mapped: tables cover {min(mapper.shape[1], alpha.shape[2])} keys, V has {Nkv}")
+    if out is None:
+        out = (torch.empty((B, heads, 64, nkv_pad), dtype=v.dtype, device=v.device),
+               torch.empty((B, heads, 64, nkv_pad), dtype=v.dtype, device=v.device))
+    vm, vo = out
+    for t in (vm, vo):
+        assert t.is_contiguous() and tuple(t.shape) == (B, heads, 64, nkv_pad) and t.dtype == v.dtype
+    a = L.VMapArgs()
+    a.dtype, a.B, a.heads, a.Nkv, a.Nkv_pad = _dt(v), B, heads, Nkv, nkv_pad
+    a.V, a.ldv, a.v_bstride = v.data_ptr(), v.stride(1), v.stride(0)
+    a.edit_of, a.E, a.steps = edit_of.data_ptr(), mapper.shape[0], alpha.shape[0]
+    a.mapper, a.ld_mapper, a.mapper_estride = mapper.data_ptr(), mapper.stride(1), mapper.stride(0)
+    a.alpha, a.alpha_step_stride, a.alpha_estride = alpha.data_ptr(), alpha.stride(0), alpha.stride(1)
+    if step_idx is not None:
+        assert step_idx.dtype == torch.int32 and step_idx.device == v.device
+        a.step_idx = step_idx.data_ptr()
+    a.Vt_mapped, a.Vt_own = vm.data_ptr(), vo.data_ptr()
+    L.check(L.lib().omg_transpose_v_mapped(C.byref(a), _stream()), "omg_transpose_v_mapped")
+    return vm, vo
 
 
 class RowMajorV:

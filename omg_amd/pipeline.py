@@ -1088,7 +1088,10 @@ class LoraMultiConceptPipeline:
                 eng.pool = None                       # the pool dies with its last graph: a later capture must open a new one
                 eng.epoch = pointer_epoch()
             win = controller._self_window() if controller is not None and hasattr(controller, "_self_window") else None
-            regime = tag + (win, tw)
+            # the cross edit's kind at this step ("borrow" / "own" / "mixed": different launches); WITHIN a kind one graph serves every
+            # step, because the edit's alpha row is selected on the device through the step counter bound below (+ its host offset)
+            ck = (controller.cross_kind(), ctl_step_offset) if hasattr(controller, "cross_kind") else None
+            regime = tag + (win, tw, ck)
             g = eng.graphs.get(regime)
             if g is not None:
                 g.replay()
@@ -1108,6 +1111,12 @@ class LoraMultiConceptPipeline:
             eng.graphs[regime] = g
             g.replay()
 
+        # the general prompt-to-prompt edit reads alpha[cur_step] on the device: cur_step == step_idx + offset from here to the end of the
+        # call (a resumed call set cur_step = first above; replays advance the host counter by one per step, as step_idx advances)
+        ctl_step_offset = 0
+        if hasattr(controller, "bind_step_counter"):
+            ctl_step_offset = controller.cur_step - first
+            controller.bind_step_counter(step_idx, ctl_step_offset)
         # ---- 8. denoising loop
         for i in range(first, S):
             run_step(i)
@@ -1138,6 +1147,8 @@ class LoraMultiConceptPipeline:
             if cache_keys and first == 0 and i >= fusion_start:         # ... and the base sample's way from there on (drop_unc0)
                 for j, k in enumerate(cache_keys):
                     stage_cache.put_base(k, i + 1, lat[2 * j: 2 * j + 1], xin[4 * j + 2: 4 * j + 3])
+        if hasattr(controller, "bind_step_counter"):
+            controller.bind_step_counter(None)      # the counter is the controller's own again (direct UNet calls)
         return lat.clone().view(n, 2, Cl, Hl, Wl)
 
 
