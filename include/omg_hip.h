@@ -491,6 +491,26 @@ int64_t omg_relu_linear_att_ws_floats(int B, int groups, int dim, int HW);
 int omg_relu_linear_att(int dtype, const void* QKV, int64_t ld, int B, int HW, int groups, int dim, float eps,
                         float* workspace, void* OUT, int64_t ldo, void* stream);
 
+/* ------------------------------------------------------------------------
+ * The convolutional part of the EfficientViT-SAM image encoder (omg_amd/efficientvit.py; the reference's
+ * models/efficientvit/backbone.py and sam.py).  NHWC fp16 / bf16, BatchNorm folded into W and bias by the caller, fp32 accumulation,
+ * one rounding.  Output size of both convolutions: (Hin - 1) / stride + 1 (kernel 3, padding 1).  GELU is the tanh form
+ * (the reference's build_act("gelu") is nn.GELU(approximate="tanh")).
+ * omg_conv3x3_nhwc_act: Y[B,Hout,Wout,Cout] = residual + gelu?(conv3x3(X[B,Hin,Win,Cin], W[Cout][3][3][Cin]) + bias), stride 1 | 2,
+ *   an implicit GEMM on the 16-bit MFMA.  Cin % 8 == 0 or Cin < 8 (the RGB stem; K is zero-padded inside the kernel); Cout % 8 == 0.
+ *   act: 0 | 1 (GELU); bias [Cout] and residual [B,Hout,Wout,Cout] may be NULL.
+ * omg_dwconv3x3_act: depthwise 3x3, stride 1 | 2, rows of ldx / ldy elements, weights [9][C] tap-major, C % 8 == 0.
+ *   act bit 0: GELU of the output; bit 1: GELU of the INPUT as it is read (the activation of the 1x1 convolution in front).
+ * omg_upsample_add_nhwc: Y[B,Hout,Wout,C] (+)= bicubic resize of X[B,Hin,Win,C] as torch.nn.functional.interpolate(mode="bicubic",
+ *   align_corners=False) computes it; accumulate == 0 overwrites Y, != 0 adds to it (sum in fp32, one rounding).  C % 8 == 0.
+ * ---------------------------------------------------------------------- */
+int omg_conv3x3_nhwc_act(int dtype, const void* X, int B, int Hin, int Win, int Cin, int Cout, int stride,
+                         const void* Wt, const void* bias, int act, const void* residual, void* Y, void* stream);
+int omg_dwconv3x3_act(int dtype, const void* X, int64_t ldx, int B, int Hin, int Win, int C, int stride,
+                      const void* Wt, const void* bias, int act, void* Y, int64_t ldy, void* stream);
+int omg_upsample_add_nhwc(int dtype, const void* X, int B, int Hin, int Win, int C, int Hout, int Wout,
+                          int accumulate, void* Y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

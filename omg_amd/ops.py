@@ -689,6 +689,49 @@ def relu_linear_att(qkv: torch.Tensor, B: int, HW: int, groups: int, dim: int, e
     return out
 
 
+def conv3x3_nhwc_act(x: torch.Tensor, w: torch.Tensor, *, stride: int = 1, bias: Optional[torch.Tensor] = None, gelu: bool = False,
+                     residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Dense 3x3 convolution (padding 1, stride 1 | 2) of NHWC ``x`` [B, H, W, Cin] with ``w`` [Cout, 3, 3, Cin] (any Cin that is a
+    multiple of 8, or below 8) -> [B, Hout, Wout, Cout]; bias, tanh GELU and residual in the epilogue.  omg_conv3x3_nhwc_act."""
+    _dev(x)
+    B, H, W, Cin = x.shape
+    Cout = w.shape[0]
+    assert x.is_contiguous() and w.is_contiguous() and w.shape == (Cout, 3, 3, Cin) and w.dtype == x.dtype
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    if out is None:
+        out = torch.empty((B, Ho, Wo, Cout), dtype=x.dtype, device=x.device)
+    assert out.shape == (B, Ho, Wo, Cout) and out.is_contiguous() and out.dtype == x.dtype
+    if residual is not None:
+        assert residual.shape == out.shape and residual.is_contiguous() and residual.dtype == x.dtype
+    L.check(L.lib().omg_conv3x3_nhwc_act(_dt(x), x.data_ptr(), B, H, W, Cin, Cout, stride, w.data_ptr(), _p(bias), int(gelu), _p(residual),
+                                         out.data_ptr(), _stream()), "omg_conv3x3_nhwc_act")
+    return out
+
+
+def dwconv3x3_act(x: torch.Tensor, taps: torch.Tensor, B: int, H: int, W: int, *, stride: int = 1, bias: Optional[torch.Tensor] = None,
+                  gelu: bool = False, gelu_in: bool = False) -> torch.Tensor:
+    """Depthwise 3x3 convolution (padding 1, stride 1 | 2) of NHWC rows ``x`` [B*H*W, C]; ``taps`` [9, C] tap-major.  ``gelu`` acts on
+    the output, ``gelu_in`` on the input as it is read.  -> [B*Hout*Wout, C].  omg_dwconv3x3_act."""
+    _dev(x)
+    M, Cc = x.shape
+    assert M == B * H * W and x.stride(1) == 1 and taps.shape == (9, Cc) and taps.is_contiguous()
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    y = torch.empty((B * Ho * Wo, Cc), dtype=x.dtype, device=x.device)
+    L.check(L.lib().omg_dwconv3x3_act(_dt(x), x.data_ptr(), x.stride(0), B, H, W, Cc, stride, taps.data_ptr(), _p(bias),
+                                      int(gelu) | (int(gelu_in) << 1), y.data_ptr(), y.stride(0), _stream()), "omg_dwconv3x3_act")
+    return y
+
+
+def upsample_add_nhwc(x: torch.Tensor, out: torch.Tensor, accumulate: bool = True) -> torch.Tensor:
+    """``out`` [B, Hout, Wout, C] (+)= bicubic resize (align_corners=False) of NHWC ``x`` [B, Hin, Win, C].  omg_upsample_add_nhwc."""
+    _dev(x)
+    B, H, W, Cc = x.shape
+    assert x.is_contiguous() and out.is_contiguous() and out.shape[0] == B and out.shape[3] == Cc and out.dtype == x.dtype
+    L.check(L.lib().omg_upsample_add_nhwc(_dt(x), x.data_ptr(), B, H, W, Cc, out.shape[1], out.shape[2], int(accumulate), out.data_ptr(),
+                                          _stream()), "omg_upsample_add_nhwc")
+    return out
+
+
 def conv_in(x_nchw: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], dtype: torch.dtype) -> torch.Tensor:
     """NCHW latents (fp32 or `dtype`) -> NHWC features in `dtype`; w: [Cout][64] from pack_conv_in_weight."""
     _dev(x_nchw)

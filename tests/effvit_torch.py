@@ -1,0 +1,129 @@
+"""A per-layer torch evaluation of omg_amd.efficientvit.EfficientViTSamImageEncoder, for the tests and tools/effvit_bench.py only.
+
+It walks the module tree of the encoder and runs every convolution as ``F.conv2d`` (NCHW) with the module's BatchNorm-folded
+weights.  Two uses:
+  * CPU, fp32 (``TorchEncoder(model, rounded=False)``, LiteMLA by oracle/litemla.py): pins the fold and the restated topology
+    against the fixture of the reference's own classes without a GPU;
+  * GPU, storage dtype (``rounded=True``, LiteMLA as the HIP module): the per-layer fallback the fused path is compared with.
+"""
+import torch
+import torch.nn.functional as F
+
+from omg_amd import efficientvit as ev
+from omg_amd.litemla import LiteMLA
+
+
+def gelu(x):
+    return F.gelu(x, approximate="tanh")
+
+
+class TorchEncoder:
+    def __init__(self, model, rounded: bool):
+        self.m, self.rounded = model, rounded
+        self.w = {}
+        for layer in model.modules():
+            if isinstance(layer, ev.ConvLayer):
+                w, b = layer.folded()
+                if rounded:
+                    dt = layer.conv.weight.dtype
+                    w, b = w.to(dt), (b.to(dt) if b is not None else None)
+                self.w[id(layer)] = (w, b)
+
+    def conv(self, layer, x):
+        w, b = self.w[id(layer)]
+        k = w.shape[-1]
+        y = F.conv2d(x, w, b, stride=layer.stride, padding=k // 2, groups=layer.cout if layer.kind == "dw" else 1)
+        return gelu(y) if layer.act else y
+
+    def litemla(self, blk, x):
+        if self.rounded:
+            return blk(x, residual=True)                     # the HIP module, NCHW in / out
+        from oracle import litemla as ol
+        sd = {k: v.float() for k, v in blk.state_dict().items()}
+        return x + ol.litemla_forward(sd, x, dim=blk.dim, scales=blk.scales)
+
+    def block(self, blk, x, shortcut):
+        if isinstance(blk, LiteMLA):
+            return self.litemla(blk, x)
+        if isinstance(blk, ev.ResBlock):
+            y = self.conv(blk.conv2, self.conv(blk.conv1, x))
+        elif isinstance(blk, ev.FusedMBConv):
+            y = self.conv(blk.point_conv, self.conv(blk.spatial_conv, x))
+        else:
+            y = self.conv(blk.point_conv, self.conv(blk.depth_conv, self.conv(blk.inverted_conv, x)))
+        return y + x if shortcut else y
+
+    def op(self, op, x):
+        if isinstance(op, ev.ConvLayer):
+            return self.conv(op, x)
+        if isinstance(op, ev.EfficientViTBlock):
+            return self.block(op.local_module.main, self.block(op.context_module.main, x, True), True)
+        return self.block(op.main, x, op.has_shortcut)
+
+    @torch.no_grad()
+    def features(self, x):
+        """NCHW in -> dict of NCHW tensors with the keys of EfficientViTSamImageEncoder.forward_features."""
+        m, cfg = self.m, self.m.cfg
+        out = {}
+        h = x
+        for s, stage in enumerate(m.backbone.stages):
+            for op in stage.op_list:
+                h = self.op(op, h)
+            out[f"stage{s}"] = h
+        acc = None
+        for i, f in enumerate(cfg.neck_fids):                # list_sum order of the reference's DAGBlock
+            t = self.conv(m.neck.input_ops[i].op_list[0], out[f"stage{f}"])
+            if t.shape[-2:] != (cfg.grid, cfg.grid):
+                t = F.interpolate(t, size=(cfg.grid, cfg.grid), mode="bicubic", align_corners=False)
+            acc = t if acc is None else acc + t
+        h = acc
+        for op in m.neck.middle.op_list:
+            h = self.op(op, h)
+        out["neck_mid"] = h
+        h = self.conv(m.neck.output_ops[0].op_list[0], h)
+        out["neck"] = h
+        out["out"] = F.layer_norm(h.permute(0, 2, 3, 1), (h.shape[1],), m.norm.weight.data, m.norm.bias.data, m.norm.eps).permute(0, 3, 1, 2)
+        return out
+
+
+@torch.no_grad()
+def seed_encoder(model, seed):
+    """Seeded weights of a full-width model, drawn on the model's device: convolutions scaled by their fan-in so that activations stay
+    O(1) through the depth, BatchNorm affine and running statistics away from the identity."""
+    dev = model.norm.weight.device
+    g = torch.Generator(device=dev).manual_seed(seed)
+    r = lambda t: torch.randn(t.shape, generator=g, device=dev, dtype=torch.float32)
+    for name, p in list(model.named_parameters()) + list(model.named_buffers()):
+        leaf = name.rsplit(".", 1)[-1]
+        if p.dim() == 4:
+            p.copy_(r(p) * (1.5 / p[0].numel()) ** 0.5)
+        elif leaf == "running_mean":
+            p.copy_(0.2 * r(p))
+        elif leaf == "running_var":
+            p.copy_(0.5 + torch.rand(p.shape, generator=g, device=dev))
+        elif leaf == "weight":
+            p.copy_(1.0 + 0.2 * r(p))
+        elif leaf == "bias":
+            p.copy_(0.1 * r(p))
+    model._packed = {}
+    for mod in model.modules():
+        if isinstance(mod, LiteMLA):
+            mod._packed = {}
+
+
+def load_fixture(path):
+    import numpy as np
+    g = np.load(path)
+    cfg = ev.EfficientViTSamConfig(width_list=tuple(g["cfg_width_list"].tolist()), depth_list=tuple(g["cfg_depth_list"].tolist()),
+                                   qkv_dim=int(g["cfg_qkv_dim"]), neck_fids=tuple(g["cfg_neck_fids"].tolist()),
+                                   head_width=int(g["cfg_head_width"]), head_depth=int(g["cfg_head_depth"]),
+                                   neck_expand=int(g["cfg_neck_expand"]), neck_middle=str(g["cfg_neck_middle"]))
+    sd = {k[3:]: torch.from_numpy(g[k]) for k in g.files if k.startswith("sd.")}
+    vec = {k: torch.from_numpy(g[k]) for k in g.files if k == "x" or k.startswith(("stage", "neck", "out"))}
+    return g, cfg, sd, vec, int(g["cfg_sub"])
+
+
+def build_from_fixture(cfg, sd, dtype, device):
+    m = ev.EfficientViTSamImageEncoder(cfg, dtype=dtype, device=device)
+    m.load_state_dict({k: (v.to(dtype) if v.dtype.is_floating_point and "running" not in k else v).to(device) for k, v in sd.items()}, strict=True)
+    return m
