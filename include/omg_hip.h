@@ -511,6 +511,38 @@ int omg_dwconv3x3_act(int dtype, const void* X, int64_t ldx, int B, int Hin, int
 int omg_upsample_add_nhwc(int dtype, const void* X, int B, int Hin, int Win, int C, int Hout, int Wout,
                           int accumulate, void* Y, void* stream);
 
+/* ------------------------------------------------------------------------
+ * SAM's mask decoder (omg_amd/sam.py: the two-way transformer, output_upscaling, the hypernetwork product) and the reference's
+ * EfficientViTSam.postprocess_masks (models/efficientvit/sam.py:225-241).  Linear layers are omg_gemm, LayerNorms omg_layernorm.
+ * omg_attn_small: O[b, q, h d + :] = softmax_k(scale Q[b, q, h d + :] . K[b, k, h d + :]) V[b, k, h d + :] for head_dim d = 16 | 32
+ *   (omg_attn_fwd is fixed at 64).  Rows of ldq / ldk / ldv / ldo elements and batches of *_bstride elements (multiples of 8, base
+ *   pointers 16-byte aligned): a column slice of a projection buffer is a valid operand.  Any Nq, Nk >= 1.  Scores, the
+ *   running-maximum softmax and P V are fp32; one rounding at the store.  No key row >= Nk is read or weighted.
+ * omg_convt2x2_ln_gelu: the scatter half of ConvTranspose2d(kernel 2, stride 2).  G [B H W][ldg] is the omg_gemm of the NHWC input
+ *   rows against the weight laid out [(dy, dx, cout)][cin] (4 Cout rows); Y [B, 2H, 2W, Cout] NHWC:
+ *     Y[b, 2y + dy, 2x + dx, :] = act(LN?(G[(b, y, x), (2 dy + dx) Cout + :] + bias))
+ *   LayerNorm over the Cout channels of a pixel (biased variance, fp32 statistics) when ln_gamma / ln_beta are given; act 0 | 1 =
+ *   erf GELU (nn.GELU()).  Cout % 8 == 0.
+ * omg_sam_mask_logits: logits[b, m, p] (fp32) = sum_c hyper[b, m, c] up[b, p, c]; hyper [B, M, C], up [B, P, C], M <= 4, C % 8 == 0,
+ *   C <= 64.  One pass over `up`.
+ * omg_sam_postprocess: low [N, Hl, Wl] fp32 -> bilinear (align_corners = False) to image_size x image_size -> crop [:in_h, :in_w]
+ *   -> bilinear to out_h x out_w, as two torch.nn.functional.interpolate calls in fp32 compute it (the intermediate is recomputed
+ *   per output pixel, not stored).  out_u8 == 0: out is fp32 [N, out_h, out_w]; 1: uint8, 1 where the value > threshold.
+ * omg_relu: Y[0:n] = X[0:n] < 0 ? 0 : X[0:n] (a NaN stays a NaN, as torch.relu), n % 8 == 0 (the decoder's MLPs; omg_gemm has no ReLU
+ *   epilogue).  Y may be X.
+ * ---------------------------------------------------------------------- */
+int omg_attn_small(int dtype, int B, int heads, int head_dim, int Nq, int Nk,
+                   const void* Q, int64_t ldq, int64_t q_bstride, const void* K, int64_t ldk, int64_t k_bstride,
+                   const void* V, int64_t ldv, int64_t v_bstride, float scale,
+                   void* O, int64_t ldo, int64_t o_bstride, void* stream);
+int omg_convt2x2_ln_gelu(int dtype, const void* G, int64_t ldg, int B, int H, int W, int Cout, const void* bias,
+                         const void* ln_gamma, const void* ln_beta, float eps, int act, void* Y, void* stream);
+int omg_sam_mask_logits(int dtype, const void* hyper, const void* up, int B, int M, int64_t P, int C,
+                        float* logits, void* stream);
+int omg_sam_postprocess(const float* low, int N, int Hl, int Wl, int image_size, int in_h, int in_w,
+                        int out_h, int out_w, float threshold, int out_u8, void* out, void* stream);
+int omg_relu(int dtype, const void* X, void* Y, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -732,6 +732,91 @@ def upsample_add_nhwc(x: torch.Tensor, out: torch.Tensor, accumulate: bool = Tru
     return out
 
 
+def attn_small(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``softmax(q k^T scale) v`` per head for head_dim 16 | 32: ``q`` [B, Nq, heads*d], ``k`` / ``v`` [B, Nk, heads*d] -> [B, Nq, heads*d].
+    Any row / batch stride that is a multiple of 8 (a column slice of a projection buffer is fine).  omg_attn_small."""
+    _dev(q)
+    B, Nq, Wd = q.shape
+    Nk = k.shape[1]
+    assert k.shape == (B, Nk, Wd) and v.shape == (B, Nk, Wd) and Wd % heads == 0 and k.dtype == q.dtype and v.dtype == q.dtype
+    assert q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1
+    if out is None:
+        out = torch.empty((B, Nq, Wd), dtype=q.dtype, device=q.device)
+    assert out.shape == (B, Nq, Wd) and out.stride(2) == 1 and out.dtype == q.dtype
+    L.check(L.lib().omg_attn_small(_dt(q), B, heads, Wd // heads, Nq, Nk, q.data_ptr(), q.stride(1), q.stride(0), k.data_ptr(), k.stride(1), k.stride(0),
+                                   v.data_ptr(), v.stride(1), v.stride(0), scale, out.data_ptr(), out.stride(1), out.stride(0), _stream()),
+            "omg_attn_small")
+    return out
+
+
+def pack_convt2x2_weight(w_iohw: torch.Tensor) -> torch.Tensor:
+    """ConvTranspose2d weight [Cin, Cout, 2, 2] -> the GEMM operand [(dy, dx, cout), cin] of :func:`convt2x2_ln_gelu`."""
+    cin, cout = w_iohw.shape[:2]
+    assert w_iohw.shape[2:] == (2, 2)
+    return w_iohw.permute(2, 3, 1, 0).reshape(4 * cout, cin).contiguous()
+
+
+def convt2x2_ln_gelu(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tensor] = None, *, ln_weight: Optional[torch.Tensor] = None,
+                     ln_bias: Optional[torch.Tensor] = None, eps: float = 1e-6, gelu: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``act(LN?(ConvTranspose2d(k=2, s=2)(x)))`` of NHWC ``x`` [B, H, W, Cin] -> [B, 2H, 2W, Cout]: omg_gemm against ``w_packed``
+    (:func:`pack_convt2x2_weight`), then omg_convt2x2_ln_gelu (scatter, bias, per-pixel LayerNorm over channels, erf GELU)."""
+    _dev(x)
+    B, H, W, Cin = x.shape
+    Cout = w_packed.shape[0] // 4
+    assert x.is_contiguous() and w_packed.shape == (4 * Cout, Cin) and w_packed.dtype == x.dtype
+    g = gemm(x.view(B * H * W, Cin), w_packed)
+    if out is None:
+        out = torch.empty((B, 2 * H, 2 * W, Cout), dtype=x.dtype, device=x.device)
+    assert out.shape == (B, 2 * H, 2 * W, Cout) and out.is_contiguous() and out.dtype == x.dtype
+    L.check(L.lib().omg_convt2x2_ln_gelu(_dt(x), g.data_ptr(), g.stride(0), B, H, W, Cout, _p(bias), _p(ln_weight), _p(ln_bias), eps, int(gelu),
+                                         out.data_ptr(), _stream()), "omg_convt2x2_ln_gelu")
+    return out
+
+
+def sam_mask_logits(hyper: torch.Tensor, up: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``logits[b, m, y, x] = sum_c hyper[b, m, c] up[b, y, x, c]`` in fp32: ``hyper`` [B, M <= 4, C], NHWC ``up`` [B, H, W, C].
+    omg_sam_mask_logits."""
+    _dev(up)
+    B, H, W, Cc = up.shape
+    M = hyper.shape[1]
+    assert hyper.shape == (B, M, Cc) and hyper.is_contiguous() and up.is_contiguous() and hyper.dtype == up.dtype
+    if out is None:
+        out = torch.empty((B, M, H, W), dtype=torch.float32, device=up.device)
+    assert out.shape == (B, M, H, W) and out.is_contiguous() and out.dtype == torch.float32
+    L.check(L.lib().omg_sam_mask_logits(_dt(up), hyper.data_ptr(), up.data_ptr(), B, M, H * W, Cc, out.data_ptr(), _stream()), "omg_sam_mask_logits")
+    return out
+
+
+def sam_postprocess(low: torch.Tensor, image_size: int, input_size: Tuple[int, int], original_size: Tuple[int, int], *,
+                    threshold: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """SAM's postprocess_masks on fp32 ``low`` [B, M, Hl, Wl]: bilinear to ``image_size``², crop to ``input_size``, bilinear to
+    ``original_size``.  ``threshold`` None -> fp32 logits; a number -> uint8 0 / 1 (logit > threshold).  omg_sam_postprocess."""
+    _dev(low)
+    if low.dtype != torch.float32:
+        raise L.OmgHipError(f"sam_postprocess takes float32 logits, not {low.dtype}")
+    B, M, Hl, Wl = low.shape
+    oh, ow = int(original_size[0]), int(original_size[1])
+    assert low.is_contiguous()
+    u8 = threshold is not None
+    if out is None:
+        out = torch.empty((B, M, oh, ow), dtype=torch.uint8 if u8 else torch.float32, device=low.device)
+    assert out.shape == (B, M, oh, ow) and out.is_contiguous() and out.dtype == (torch.uint8 if u8 else torch.float32)
+    L.check(L.lib().omg_sam_postprocess(low.data_ptr(), B * M, Hl, Wl, int(image_size), int(input_size[0]), int(input_size[1]), oh, ow,
+                                        float(threshold) if u8 else 0.0, int(u8), out.data_ptr(), _stream()), "omg_sam_postprocess")
+    return out
+
+
+def relu(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``max(x, 0)`` of a contiguous tensor whose size is a multiple of 8 (``out=x`` for in place).  omg_relu."""
+    _dev(x)
+    assert x.is_contiguous()
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.is_contiguous() and out.shape == x.shape and out.dtype == x.dtype
+    L.check(L.lib().omg_relu(_dt(x), x.data_ptr(), out.data_ptr(), x.numel(), _stream()), "omg_relu")
+    return out
+
+
 def conv_in(x_nchw: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], dtype: torch.dtype) -> torch.Tensor:
     """NCHW latents (fp32 or `dtype`) -> NHWC features in `dtype`; w: [Cout][64] from pack_conv_in_weight."""
     _dev(x_nchw)
