@@ -543,6 +543,28 @@ int omg_sam_postprocess(const float* low, int N, int Hl, int Wl, int image_size,
                         int out_h, int out_w, float threshold, int out_u8, void* out, void* stream);
 int omg_relu(int dtype, const void* X, void* Y, int64_t n, void* stream);
 
+/* ------------------------------------------------------------------------
+ * SAM's ViT image encoder (omg_amd/sam_vit.py: segment_anything's ImageEncoderViT).  Linear layers are omg_gemm, LayerNorms
+ * omg_layernorm, the neck's 3x3 convolution omg_conv3x3_nhwc_act.
+ * omg_attn_relpos: softmax attention per head with the decomposed relative-position bias, read straight from the fused QKV
+ *   projection.  qkv [B H W][ld]: rows in image order, columns q | k | v, each heads * head_dim wide and head-major; out [B H W][ldo],
+ *   head-major; ld, ldo multiples of 8, base pointers 16-byte aligned.  head_dim 64 | 80.
+ *     score((qy, qx), (ky, kx)) = scale q.k + q.rel_h[qy - ky + Sh - 1] + q.rel_w[qx - kx + Sw - 1]
+ *   with the bias terms on the UNSCALED q; rel_h [2 Sh - 1][head_dim], rel_w [2 Sw - 1][head_dim], contiguous, in the storage dtype.
+ *   Scores, bias, softmax and P V are fp32 (16-bit MFMA operands); neither scores nor bias are written to memory.
+ *   window == 0: the keys are all H W tokens of the sample, Sh = H, Sw = W.  Any H, W >= 1 up to what the bias tables may take of
+ *     LDS: H + W <= 83, or W == 64 (a key tile is one image row) and H <= 335.
+ *   window == S (S S <= 256): the grid is cut into ceil(H / S) x ceil(W / S) windows from the top left; a query attends to the S S
+ *     positions of its own window with offsets taken inside the window (Sh = Sw = S).  A position beyond the H x W grid is a real key
+ *     with k | v = pad_kv [2 heads head_dim] (null: zeros) — what zero padding after the norm gives: the k and v slices of the QKV
+ *     bias.  Queries beyond the grid are not computed.
+ *   B, H or W == 0: nothing to do.
+ * omg_gelu_erf: Y[0:n] = erf GELU of X[0:n] (nn.GELU()), n % 8 == 0.  Y may be X.
+ * ---------------------------------------------------------------------- */
+int omg_attn_relpos(int dtype, int B, int H, int W, int heads, int head_dim, int window, const void* qkv, int64_t ld,
+                    const void* rel_h, const void* rel_w, const void* pad_kv, float scale, void* out, int64_t ldo, void* stream);
+int omg_gelu_erf(int dtype, const void* X, void* Y, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,11 +3,19 @@ replacement, region-masked noise fusion).  See DESIGN.md."""
 __version__ = "0.1.0"
 
 _SAM = ("SamPromptEncoder", "SamMaskDecoder", "EfficientViTSam", "EfficientViTSamPredictor", "efficientvit_sam")
-__all__ = list(_SAM)
+_SAM_VIT = ("SamImageEncoderViT",)
+_SEGMENT_ANYTHING = ("Sam", "SamPredictor", "ResizeLongestSide", "build_sam", "build_sam_vit_h", "build_sam_vit_l", "build_sam_vit_b", "sam_model_registry")
+__all__ = list(_SAM) + list(_SAM_VIT) + list(_SEGMENT_ANYTHING)
 
 
 def __getattr__(name):          # the segmenter's public names, imported on first use (omg_amd.sam pulls in torch and the kernels' bindings)
     if name in _SAM:
         from . import sam
         return getattr(sam, name)
+    if name in _SAM_VIT:
+        from . import sam_vit
+        return getattr(sam_vit, name)
+    if name in _SEGMENT_ANYTHING:
+        from . import segment_anything
+        return getattr(segment_anything, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

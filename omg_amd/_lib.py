@@ -176,6 +176,8 @@ SYMBOLS = {
     "omg_sam_mask_logits": (c_i32, [c_i32, c_vp, c_vp, c_i32, c_i32, c_i64, c_i32, c_vp, c_vp]),
     "omg_sam_postprocess": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_i32, c_vp, c_vp]),
     "omg_relu": (c_i32, [c_i32, c_vp, c_vp, c_i64, c_vp]),
+    "omg_attn_relpos": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_f32, c_vp, c_i64, c_vp]),
+    "omg_gelu_erf": (c_i32, [c_i32, c_vp, c_vp, c_i64, c_vp]),
     "omg_debug_set_glds": (None, [c_i32]),
     "omg_debug_set_gemm_variant": (None, [c_i32]),
     "omg_debug_choose_variant": (c_i32, [c_i32, c_i32, c_i32, c_i32]),

@@ -817,6 +817,42 @@ def relu(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     return out
 
 
+def attn_relpos(qkv: torch.Tensor, B: int, H: int, W: int, heads: int, rel_h: torch.Tensor, rel_w: torch.Tensor, scale: float, *,
+                window: int = 0, pad_kv: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Softmax attention per head with SAM's decomposed relative-position bias on the fused projection ``qkv`` [B*H*W, 3*heads*d]
+    (rows in image order, columns q | k | v, head-major; any row stride that is a multiple of 8) -> [B*H*W, heads*d]; d = 64 | 80.
+    ``window`` 0: global, ``rel_h`` [2H-1, d], ``rel_w`` [2W-1, d].  ``window`` S: the S x S windows from the top left, tables
+    [2S-1, d]; positions beyond the grid are keys with k | v = ``pad_kv`` [2*heads*d] (None: zeros).  omg_attn_relpos."""
+    _dev(qkv)
+    M, Wd = qkv.shape
+    assert M == B * H * W and Wd % (3 * heads) == 0 and qkv.stride(1) == 1
+    d = Wd // (3 * heads)
+    S = (window, window) if window else (H, W)
+    for name, t, n in (("rel_h", rel_h, S[0]), ("rel_w", rel_w, S[1])):
+        if tuple(t.shape) != (2 * n - 1, d):
+            raise L.OmgHipError(f"attn_relpos: {name} is {tuple(t.shape)}, the layer needs ({2 * n - 1}, {d}) (no interpolation of the table)")
+        assert t.is_contiguous() and t.dtype == qkv.dtype and t.is_cuda
+    if pad_kv is not None:
+        assert pad_kv.shape == (2 * heads * d,) and pad_kv.is_contiguous() and pad_kv.dtype == qkv.dtype and pad_kv.is_cuda
+    if out is None:
+        out = torch.empty((M, heads * d), dtype=qkv.dtype, device=qkv.device)
+    assert out.shape == (M, heads * d) and out.stride(1) == 1 and out.dtype == qkv.dtype
+    L.check(L.lib().omg_attn_relpos(_dt(qkv), B, H, W, heads, d, window, qkv.data_ptr(), qkv.stride(0), rel_h.data_ptr(), rel_w.data_ptr(),
+                                    _p(pad_kv), scale, out.data_ptr(), out.stride(0), _stream()), "omg_attn_relpos")
+    return out
+
+
+def gelu_erf(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """erf GELU (``nn.GELU()``) of a contiguous tensor whose size is a multiple of 8 (``out=x`` for in place).  omg_gelu_erf."""
+    _dev(x)
+    assert x.is_contiguous()
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.is_contiguous() and out.shape == x.shape and out.dtype == x.dtype
+    L.check(L.lib().omg_gelu_erf(_dt(x), x.data_ptr(), out.data_ptr(), x.numel(), _stream()), "omg_gelu_erf")
+    return out
+
+
 def conv_in(x_nchw: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], dtype: torch.dtype) -> torch.Tensor:
     """NCHW latents (fp32 or `dtype`) -> NHWC features in `dtype`; w: [Cout][64] from pack_conv_in_weight."""
     _dev(x_nchw)
