@@ -484,9 +484,15 @@ int omg_attn_apply_probs(int dtype, const void* P, const void* V, int64_t ldv, i
  *   elements (so that it can read a column slice of the fused qkv buffer), weights [ksize*ksize][C] tap-major, stride 1, same padding.
  * omg_relu_linear_att: relu_linear_att (ops.py:405-441) in fp32 as the reference computes it.  QKV [B*HW][ld]: group g holds its
  *   q | k | v (dim each) at columns 3 dim g; OUT [B*HW][ldo]: group g at columns dim g.  dim in {8, 16, 32}.
+ * omg_litemla_aggreg: one scale of the aggregation in one launch (ops.py:376-391): the depthwise convolution of omg_dwconv2d (fp32,
+ *   rounded once to the storage dtype) and the 1x1 convolution with C / dim groups behind it on the 16-bit MFMA (fp32 accumulation,
+ *   one rounding).  Wg [C][dim] is the grouped convolution's own weight.  dim in {16, 32}, C a multiple of dim.  Y may be another
+ *   column slice of the buffer X is a slice of (ldx == ldy, disjoint columns); any other overlap is refused.
  * ---------------------------------------------------------------------- */
 int omg_dwconv2d(int dtype, const void* X, int64_t ldx, int B, int H, int W, int C, int ksize,
                  const void* Wt, const void* bias, void* Y, int64_t ldy, void* stream);
+int omg_litemla_aggreg(int dtype, const void* X, int64_t ldx, int B, int H, int W, int C, int ksize, int dim,
+                       const void* Wt, const void* Wg, void* Y, int64_t ldy, void* stream);
 int64_t omg_relu_linear_att_ws_floats(int B, int groups, int dim, int HW);
 int omg_relu_linear_att(int dtype, const void* QKV, int64_t ld, int B, int HW, int groups, int dim, float eps,
                         float* workspace, void* OUT, int64_t ldo, void* stream);

@@ -2,7 +2,8 @@
 replacement, region-masked noise fusion).  See DESIGN.md."""
 __version__ = "0.1.0"
 
-_SAM = ("SamPromptEncoder", "SamMaskDecoder", "EfficientViTSam", "EfficientViTSamPredictor", "efficientvit_sam")
+_SAM = ("SamPromptEncoder", "SamMaskDecoder", "EfficientViTSam", "EfficientViTSamPredictor", "efficientvit_sam", "efficientvit_sam_xl0",
+        "efficientvit_sam_xl1", "create_sam_model", "set_norm_eps", "EfficientViTSamConfig", "EfficientViTSamImageEncoder")
 _SAM_VIT = ("SamImageEncoderViT",)
 _SEGMENT_ANYTHING = ("Sam", "SamPredictor", "ResizeLongestSide", "build_sam", "build_sam_vit_h", "build_sam_vit_l", "build_sam_vit_b", "sam_model_registry")
 __all__ = list(_SAM) + list(_SAM_VIT) + list(_SEGMENT_ANYTHING)

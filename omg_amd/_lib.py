@@ -165,6 +165,7 @@ SYMBOLS = {
     "omg_attn_probs": (c_i32, [C.POINTER(AttnArgs), c_vp, c_vp]),
     "omg_attn_apply_probs": (c_i32, [c_i32, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_i64, c_vp]),
     "omg_dwconv2d": (c_i32, [c_i32, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "omg_litemla_aggreg": (c_i32, [c_i32, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "omg_relu_linear_att_ws_floats": (c_i64, [c_i32, c_i32, c_i32, c_i32]),
     "omg_relu_linear_att": (c_i32, [c_i32, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_i64, c_vp]),
     "omg_conv3x3_nhwc_act": (c_i32, [c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),

@@ -12,7 +12,8 @@ with the caller), NCHW ``[B, 256, 64, 64]`` out; NHWC rows inside, as LiteMLA.
                                                                    inverted_conv in front of it while it loads (the reference's "gelu"
                                                                    is the tanh form, models/nn/act.py; omg_gemm's GELU epilogue is the
                                                                    erf form of GEGLU, so the activation cannot ride on that GEMM)
-  EfficientViTBlock.context_module                              -> omg_amd.litemla.LiteMLA, unchanged
+  EfficientViTBlock.context_module                              -> omg_amd.litemla.LiteMLA ("att": scales (5,); "att@3": scales (3,));
+                                                                   the xl recipes run its aggregation as omg_litemla_aggreg
   SamNeck fusion  sum_i upsample(conv1x1(stage_i))              -> omg_gemm + omg_upsample_add_nhwc (bicubic, as UpSampleLayer's default)
   LayerNorm2d                                                   -> omg_layernorm on the NHWC rows
 
@@ -34,8 +35,9 @@ from .litemla import LiteMLA
 
 @dataclass(frozen=True)
 class EfficientViTSamConfig:
-    """The l-series recipe: an EfficientViTLargeBackbone (stage s: one stride-2 block, then depth_list[s] blocks of block_list[s]) and a
-    SamNeck over the stages ``neck_fids``."""
+    """An EfficientViTLargeBackbone (stage s: one stride-2 block, then depth_list[s] blocks of block_list[s]) and a SamNeck over the
+    stages ``neck_fids``.  The defaults are the l-series'; ``xl0()`` / ``xl1()`` are the six-stage recipes of the reference's
+    efficientvit_sam_xl0 / _xl1 (models/efficientvit/sam.py:604-653)."""
     width_list: Tuple[int, ...]
     depth_list: Tuple[int, ...]
     block_list: Tuple[str, ...] = ("res", "fmb", "fmb", "mb", "att")
@@ -49,17 +51,34 @@ class EfficientViTSamConfig:
     neck_middle: str = "fmb"
     out_dim: int = 256
     grid: int = 64                                # the neck resizes every input to grid x grid
+    fused_aggreg: bool = False                    # LiteMLA's aggregation as omg_litemla_aggreg (no block-diagonal weight image)
 
     @staticmethod
     def variant(name: str) -> "EfficientViTSamConfig":
         name = name.lower()
         if name.startswith("xl"):
-            raise L.OmgHipError(f"EfficientViT-SAM {name}: the xl variants (six stages, att@3 blocks, 1024^2 input) are not built; use l0, l1 or l2")
+            raise L.OmgHipError(f"EfficientViT-SAM {name}: the xl variants (six stages, att@3 blocks, 1024^2 input) are not built by name "
+                                "here; use efficientvit_sam_xl0 / efficientvit_sam_xl1 / create_sam_model, or EfficientViTSamConfig.xl0() / .xl1()")
         depth = {"l0": ((1, 1, 1, 4, 4), 4), "l1": ((1, 1, 1, 6, 6), 8), "l2": ((1, 2, 2, 8, 8), 12)}
         if name not in depth:
             raise L.OmgHipError(f"unknown EfficientViT-SAM variant {name!r}; use l0, l1 or l2")
         d, hd = depth[name]
         return EfficientViTSamConfig(width_list=(32, 64, 128, 256, 512), depth_list=d, head_depth=hd)
+
+    @staticmethod
+    def _xl(depth_list, head_depth) -> "EfficientViTSamConfig":
+        return EfficientViTSamConfig(width_list=(32, 64, 128, 256, 512, 1024), depth_list=depth_list,
+                                     block_list=("res", "fmb", "fmb", "fmb", "att@3", "att@3"), expand_list=(1, 4, 4, 4, 4, 6),
+                                     fewer_norm_list=(False, False, False, False, True, True), neck_fids=(5, 4, 3), head_depth=head_depth,
+                                     neck_expand=4, fused_aggreg=True)
+
+    @staticmethod
+    def xl0() -> "EfficientViTSamConfig":
+        return EfficientViTSamConfig._xl((0, 1, 1, 2, 3, 3), 6)
+
+    @staticmethod
+    def xl1() -> "EfficientViTSamConfig":
+        return EfficientViTSamConfig._xl((1, 2, 2, 4, 6, 6), 12)
 
 
 # ---------------------------------------------------------------------------------------------- the reference's module tree, as holders of weights
@@ -152,9 +171,9 @@ class ResidualBlock(nn.Module):
 
 
 class EfficientViTBlock(nn.Module):
-    def __init__(self, c, dim, expand, dtype, device):
+    def __init__(self, c, dim, expand, dtype, device, scales=(5,), aggreg="gemm"):
         super().__init__()
-        self.context_module = ResidualBlock(LiteMLA(c, c, dim=dim, norm=(None, "bn2d"), scales=(5,), dtype=dtype, device=device), True)
+        self.context_module = ResidualBlock(LiteMLA(c, c, dim=dim, norm=(None, "bn2d"), scales=scales, dtype=dtype, device=device, aggreg=aggreg), True)
         self.local_module = ResidualBlock(MBConv(c, c, 1, expand, True, dtype, device), True)
 
 
@@ -185,13 +204,14 @@ class _Backbone(nn.Module):
         cin = w[0]
         for s in range(1, len(w)):
             kind, fewer = cfg.block_list[s], cfg.fewer_norm_list[s]
-            if kind not in ("res", "fmb", "mb", "att"):
-                raise L.OmgHipError(f"EfficientViT: block type {kind!r} is not built (l0 / l1 / l2 use res, fmb, mb, att)")
+            if kind not in ("res", "fmb", "mb", "att", "att@3"):
+                raise L.OmgHipError(f"EfficientViT: block type {kind!r} is not built (the l and xl series use res, fmb, mb, att, att@3)")
             stage = [ResidualBlock(_local_block(kind if kind in ("mb", "fmb") else "mb", cin, w[s], 2, cfg.expand_list[s] * 4, fewer, dtype, device), False)]
             cin = w[s]
             for _ in range(d[s]):
-                if kind == "att":
-                    stage.append(EfficientViTBlock(cin, cfg.qkv_dim, cfg.expand_list[s], dtype, device))
+                if kind in ("att", "att@3"):
+                    stage.append(EfficientViTBlock(cin, cfg.qkv_dim, cfg.expand_list[s], dtype, device, scales=(3,) if kind == "att@3" else (5,),
+                                                   aggreg="fused" if cfg.fused_aggreg else "gemm"))
                 else:
                     stage.append(ResidualBlock(_local_block(kind, cin, cin, 1, cfg.expand_list[s], fewer, dtype, device), True))
             stages.append(OpSequential(stage))

@@ -9,6 +9,8 @@ so a checkpoint of the reference's module loads key for key.  MI355X-first layou
   per scale: depthwise s x s conv  -> omg_dwconv2d reading that column slice                                      (ops.py:376-384)
              1x1 conv, 3*heads groups -> omg_gemm with the block-diagonal weight, writing the next 3T columns     (ops.py:385-391)
                                        (``torch.cat`` of :449 never happens; the zero blocks add exact zeros)
+             aggreg="fused": both      -> omg_litemla_aggreg, one launch, the grouped weight as it is (no [3T, 3T] image: at
+                                       T = 1024, dim = 32 that image is 18.9 MB of which 0.2 MB are weights); dim 16 | 32
   relu_linear_att (fp32)           -> omg_relu_linear_att                                                         (ops.py:405-441)
   proj 1x1 conv + BatchNorm2d(eval) -> omg_gemm with the norm folded into weight and bias                         (ops.py:395-402, :452)
 
@@ -52,14 +54,17 @@ class _ConvLayer(nn.Module):
 class LiteMLA(nn.Module):
     def __init__(self, in_channels: int, out_channels: int, heads: Optional[int] = None, heads_ratio: float = 1.0, dim: int = 8,
                  use_bias=False, norm=(None, "bn2d"), act_func=(None, None), kernel_func: str = "relu", scales: Sequence[int] = (5,),
-                 eps: float = 1.0e-15, dtype=torch.float16, device=None):
+                 eps: float = 1.0e-15, dtype=torch.float16, device=None, aggreg: str = "gemm"):
         super().__init__()
         if use_bias not in (False, (False, False)) or tuple(act_func) != (None, None) or kernel_func != "relu" or norm[0] is not None \
                 or norm[1] not in (None, "bn2d"):
             raise L.OmgHipError("LiteMLA: only the configuration EfficientViT uses is built (no bias, ReLU kernel, norm=(None, 'bn2d' | None))")
         if dim not in (8, 16, 32):
             raise L.OmgHipError("LiteMLA: dim must be 8, 16 or 32")
+        if aggreg not in ("gemm", "fused"):
+            raise L.OmgHipError("LiteMLA: aggreg must be 'gemm' or 'fused'")
         self.eps, self.dim, self.scales = eps, dim, tuple(scales)
+        self.fused_aggreg = aggreg == "fused" and dim in (16, 32)      # omg_litemla_aggreg has no dim = 8: that stays on the GEMM
         self.heads = heads or int(in_channels // dim * heads_ratio)
         T = self.heads * dim
         self.total_dim, self.in_channels, self.out_channels = T, in_channels, out_channels
@@ -87,9 +92,13 @@ class LiteMLA(nn.Module):
             return self._packed
         T3, d = 3 * self.total_dim, self.dim
         dt = self.qkv.conv.weight.dtype
-        pk = {"wqkv": self.qkv.conv.weight.data.reshape(T3, self.in_channels).contiguous(), "taps": [], "wbd": []}
+        pk = {"wqkv": self.qkv.conv.weight.data.reshape(T3, self.in_channels).contiguous(), "taps": []}
+        pk["wg" if self.fused_aggreg else "wbd"] = []
         for (dw, pw), s in zip(self.aggreg, self.scales):
             pk["taps"].append(dw.weight.data.reshape(T3, s * s).t().contiguous())                    # [s*s, 3T] tap-major
+            if self.fused_aggreg:
+                pk["wg"].append(pw.weight.data.reshape(T3, d).contiguous())                           # [3T, dim]: a view of the checkpoint's tensor
+                continue
             w = pw.weight.data.reshape(T3 // d, d, d)                                                 # [group, out, in]
             pk["wbd"].append(torch.block_diag(*w.float().unbind(0)).to(dt).contiguous())              # [3T, 3T], exact zeros off the blocks
         w = self.proj.conv.weight.data.reshape(self.out_channels, -1).float()
@@ -114,6 +123,9 @@ class LiteMLA(nn.Module):
         buf = torch.empty((M, T3 * (1 + n)), dtype=x.dtype, device=x.device)
         ops.gemm(x2, pk["wqkv"], out=buf[:, :T3])
         for i, s in enumerate(self.scales):
+            if self.fused_aggreg:
+                ops.litemla_aggreg(buf[:, :T3], pk["taps"][i], pk["wg"][i], B, H, W, s, self.dim, out=buf[:, T3 * (i + 1):T3 * (i + 2)])
+                continue
             t = ops.dwconv2d(buf[:, :T3], pk["taps"][i], B, H, W, s)
             ops.gemm(t, pk["wbd"][i], out=buf[:, T3 * (i + 1):T3 * (i + 2)])
         att = ops.relu_linear_att(buf, B, H * W, self.heads * (1 + n), self.dim, self.eps)

@@ -671,9 +671,39 @@ def dwconv2d(x: torch.Tensor, taps: torch.Tensor, B: int, H: int, W: int, ksize:
     M, Cc = x.shape
     assert M == B * H * W and x.stride(1) == 1 and taps.shape == (ksize * ksize, Cc) and taps.is_contiguous()
     y = torch.empty((M, Cc), dtype=x.dtype, device=x.device)
+    t0 = _PROF.begin() if _PROF is not None else None
     L.check(L.lib().omg_dwconv2d(_dt(x), x.data_ptr(), x.stride(0), B, H, W, Cc, ksize, taps.data_ptr(), _p(bias), y.data_ptr(), y.stride(0), _stream()),
             "omg_dwconv2d")
+    if _PROF is not None:
+        _PROF.end("dwconv2d", 2.0 * M * Cc * ksize * ksize, t0, ("dwconv2d", M, Cc, ksize))
     return y
+
+
+def litemla_aggreg(x: torch.Tensor, taps: torch.Tensor, wg: torch.Tensor, B: int, H: int, W: int, ksize: int, dim: int,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One scale of LiteMLA's aggregation in one launch: the depthwise ``ksize x ksize`` convolution of ``dwconv2d`` (rounded once to
+    the storage dtype) and the 1x1 convolution with ``C / dim`` groups behind it.  ``x`` [B*H*W, C] NHWC rows (any row stride);
+    ``taps`` [ksize*ksize, C]; ``wg`` [C, dim], the grouped convolution's own weight; ``out`` may be another column slice of the buffer
+    ``x`` is a slice of.  dim 16 | 32.  omg_litemla_aggreg."""
+    _dev(x)
+    M, Cc = x.shape
+    assert M == B * H * W and x.stride(1) == 1 and taps.shape == (ksize * ksize, Cc) and taps.is_contiguous()
+    assert wg.shape == (Cc, dim) and wg.is_contiguous() and taps.dtype == x.dtype and wg.dtype == x.dtype
+    if out is None:
+        out = torch.empty((M, Cc), dtype=x.dtype, device=x.device)
+    assert out.shape == (M, Cc) and out.stride(1) == 1 and out.dtype == x.dtype and out.device == x.device
+    es = x.element_size()
+    x0, y0 = x.data_ptr(), out.data_ptr()
+    if M and x0 < y0 + ((M - 1) * out.stride(0) + Cc) * es and y0 < x0 + ((M - 1) * x.stride(0) + Cc) * es:
+        # the same buffer: the same rows, and columns that x does not have
+        dcol = abs(y0 - x0) // es % max(x.stride(0), 1)
+        assert x.stride(0) == out.stride(0) and Cc <= dcol <= x.stride(0) - Cc, "litemla_aggreg: out overlaps x"
+    t0 = _PROF.begin() if _PROF is not None else None
+    L.check(L.lib().omg_litemla_aggreg(_dt(x), x0, x.stride(0), B, H, W, Cc, ksize, dim, taps.data_ptr(), wg.data_ptr(), y0, out.stride(0),
+                                       _stream()), "omg_litemla_aggreg")
+    if _PROF is not None:
+        _PROF.end("litemla_aggreg", 2.0 * M * Cc * (ksize * ksize + dim), t0, ("litemla_aggreg", M, Cc, ksize, dim))
+    return out
 
 
 def relu_linear_att(qkv: torch.Tensor, B: int, HW: int, groups: int, dim: int, eps: float) -> torch.Tensor:
@@ -684,8 +714,11 @@ def relu_linear_att(qkv: torch.Tensor, B: int, HW: int, groups: int, dim: int, e
     assert M == B * HW and Cc == groups * 3 * dim and qkv.stride(1) == 1
     out = torch.empty((M, groups * dim), dtype=qkv.dtype, device=qkv.device)
     ws = torch.empty((int(L.lib().omg_relu_linear_att_ws_floats(B, groups, dim, HW)),), dtype=torch.float32, device=qkv.device)
+    t0 = _PROF.begin() if _PROF is not None else None
     L.check(L.lib().omg_relu_linear_att(_dt(qkv), qkv.data_ptr(), qkv.stride(0), B, HW, groups, dim, eps, ws.data_ptr(), out.data_ptr(), out.stride(0),
                                         _stream()), "omg_relu_linear_att")
+    if _PROF is not None:
+        _PROF.end("relu_linear_att", 4.0 * M * groups * dim * (dim + 1), t0, ("relu_linear_att", M, groups, dim))
     return out
 
 
@@ -703,8 +736,11 @@ def conv3x3_nhwc_act(x: torch.Tensor, w: torch.Tensor, *, stride: int = 1, bias:
     assert out.shape == (B, Ho, Wo, Cout) and out.is_contiguous() and out.dtype == x.dtype
     if residual is not None:
         assert residual.shape == out.shape and residual.is_contiguous() and residual.dtype == x.dtype
+    t0 = _PROF.begin() if _PROF is not None else None
     L.check(L.lib().omg_conv3x3_nhwc_act(_dt(x), x.data_ptr(), B, H, W, Cin, Cout, stride, w.data_ptr(), _p(bias), int(gelu), _p(residual),
                                          out.data_ptr(), _stream()), "omg_conv3x3_nhwc_act")
+    if _PROF is not None:
+        _PROF.end("conv3x3_nhwc", 2.0 * B * Ho * Wo * Cout * 9 * Cin, t0, ("conv3x3_nhwc", B * Ho * Wo, Cout, 9 * Cin, stride))
     return out
 
 
@@ -717,8 +753,11 @@ def dwconv3x3_act(x: torch.Tensor, taps: torch.Tensor, B: int, H: int, W: int, *
     assert M == B * H * W and x.stride(1) == 1 and taps.shape == (9, Cc) and taps.is_contiguous()
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     y = torch.empty((B * Ho * Wo, Cc), dtype=x.dtype, device=x.device)
+    t0 = _PROF.begin() if _PROF is not None else None
     L.check(L.lib().omg_dwconv3x3_act(_dt(x), x.data_ptr(), x.stride(0), B, H, W, Cc, stride, taps.data_ptr(), _p(bias),
                                       int(gelu) | (int(gelu_in) << 1), y.data_ptr(), y.stride(0), _stream()), "omg_dwconv3x3_act")
+    if _PROF is not None:
+        _PROF.end("dwconv3x3", 2.0 * B * Ho * Wo * Cc * 9, t0, ("dwconv3x3", B * Ho * Wo, Cc, stride))
     return y
 
 
@@ -727,8 +766,11 @@ def upsample_add_nhwc(x: torch.Tensor, out: torch.Tensor, accumulate: bool = Tru
     _dev(x)
     B, H, W, Cc = x.shape
     assert x.is_contiguous() and out.is_contiguous() and out.shape[0] == B and out.shape[3] == Cc and out.dtype == x.dtype
+    t0 = _PROF.begin() if _PROF is not None else None
     L.check(L.lib().omg_upsample_add_nhwc(_dt(x), x.data_ptr(), B, H, W, Cc, out.shape[1], out.shape[2], int(accumulate), out.data_ptr(),
                                           _stream()), "omg_upsample_add_nhwc")
+    if _PROF is not None:
+        _PROF.end("upsample_add", 32.0 * out.numel(), t0, ("upsample_add", H, W, Cc))
     return out
 
 

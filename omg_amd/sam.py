@@ -27,9 +27,12 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ops
+from . import efficientvit as _ev
 from .efficientvit import EfficientViTSamConfig, EfficientViTSamImageEncoder
+from .litemla import LiteMLA
 
-__all__ = ["SamPromptEncoder", "SamMaskDecoder", "EfficientViTSam", "EfficientViTSamPredictor", "efficientvit_sam"]
+__all__ = ["SamPromptEncoder", "SamMaskDecoder", "EfficientViTSam", "EfficientViTSamPredictor", "efficientvit_sam", "efficientvit_sam_xl0",
+           "efficientvit_sam_xl1", "create_sam_model", "set_norm_eps", "EfficientViTSamConfig", "EfficientViTSamImageEncoder"]
 
 
 def _param(shape, dtype, device):
@@ -195,7 +198,7 @@ class _MLP(nn.Module):
 
 
 class SamMaskDecoder(nn.Module):
-    LN_EPS = 1e-5            # nn.LayerNorm's default; LayerNorm2d of output_upscaling uses 1e-6
+    LN_EPS = 1e-5            # nn.LayerNorm's default (set_norm_eps overrides it per instance); LayerNorm2d of output_upscaling uses 1e-6
 
     def __init__(self, transformer_dim: int = 256, num_multimask_outputs: int = 3, depth: int = 2, num_heads: int = 8, mlp_dim: int = 2048,
                  iou_head_depth: int = 3, iou_head_hidden_dim: int = 256, dtype=torch.float16, device=None):
@@ -376,6 +379,64 @@ def efficientvit_sam(name: str, dtype=torch.float16, device=None) -> EfficientVi
     return EfficientViTSam(EfficientViTSamImageEncoder(cfg, dtype=dtype, device=device),
                            SamPromptEncoder(256, (64, 64), (1024, 1024), 16, dtype=dtype, device=device),
                            SamMaskDecoder(256, 3, 2, 8, 2048, 3, 256, dtype=dtype, device=device), image_size=(1024, 512))
+
+
+def _build(cfg: EfficientViTSamConfig, image_size: int, dtype, device) -> EfficientViTSam:
+    """build_efficientvit_sam of the reference (sam.py:520-544): the same prompt encoder and mask decoder behind every image encoder."""
+    return EfficientViTSam(EfficientViTSamImageEncoder(cfg, dtype=dtype, device=device),
+                           SamPromptEncoder(256, (64, 64), (1024, 1024), 16, dtype=dtype, device=device),
+                           SamMaskDecoder(256, 3, 2, 8, 2048, 3, 256, dtype=dtype, device=device), image_size=(1024, image_size))
+
+
+def efficientvit_sam_xl0(image_size: int = 1024, dtype=torch.float16, device=None) -> EfficientViTSam:
+    """The reference's efficientvit_sam_xl0 (sam.py:604-627): six stages, att@3 blocks, a 1024 x 1024 encoder input."""
+    return _build(EfficientViTSamConfig.xl0(), image_size, dtype, device)
+
+
+def efficientvit_sam_xl1(image_size: int = 1024, dtype=torch.float16, device=None) -> EfficientViTSam:
+    """The reference's efficientvit_sam_xl1 (sam.py:630-653), the segmenter every script of the reference builds."""
+    return _build(EfficientViTSamConfig.xl1(), image_size, dtype, device)
+
+
+def set_norm_eps(model: nn.Module, eps: float) -> None:
+    """set_norm_eps of the reference (models/nn/norm.py:153-157) on this package's holders: every BatchNorm, the encoder's LayerNorm2d,
+    LiteMLA's proj.norm and the two-way transformer's LayerNorms get ``eps``.  output_upscaling's LayerNorm2d keeps its 1e-6: it is
+    segment_anything's class, no nn.LayerNorm, and the reference's call leaves it alone.  BatchNorm is folded when the packed weights
+    are built, so every packed-weight cache is dropped."""
+    for m in model.modules():
+        if isinstance(m, (_ev._BatchNorm, _ev._LayerNorm)):
+            m.eps = eps
+        elif isinstance(m, LiteMLA):
+            if m.proj.norm is not None:
+                m.proj.norm.eps = eps
+            m._packed = {}
+        elif isinstance(m, EfficientViTSamImageEncoder):
+            m._packed = {}
+        elif isinstance(m, SamMaskDecoder):
+            m.LN_EPS = eps
+            m._packed = None
+
+
+def create_sam_model(name: str, pretrained: bool = True, weight_url: Optional[str] = None, dtype=torch.float16, device=None) -> EfficientViTSam:
+    """create_sam_model of the reference (sam_model_zoo.py:26-53): ``name`` up to its first "-" is l0 | l1 | l2 | xl0 | xl1; the model is
+    built, every norm's eps is set to 1e-6, and with ``pretrained`` the checkpoint at ``weight_url`` is loaded (there is no model zoo
+    directory to fall back on)."""
+    builders = {"l0": lambda: efficientvit_sam("l0", dtype=dtype, device=device), "l1": lambda: efficientvit_sam("l1", dtype=dtype, device=device),
+                "l2": lambda: efficientvit_sam("l2", dtype=dtype, device=device),
+                "xl0": lambda: efficientvit_sam_xl0(dtype=dtype, device=device), "xl1": lambda: efficientvit_sam_xl1(dtype=dtype, device=device)}
+    model_id = name.split("-")[0]
+    if model_id not in builders:
+        raise ValueError(f"Do not find {name} in the model zoo. List of models: {list(builders)}")
+    if pretrained and weight_url is None:
+        raise ValueError(f"Do not find the pretrained weight of {name}: pass weight_url")
+    model = builders[model_id]()
+    set_norm_eps(model, 1e-6)
+    if pretrained:
+        weight = torch.load(weight_url, map_location="cpu")
+        if "state_dict" in weight:
+            weight = weight["state_dict"]
+        model.load_state_dict(weight)
+    return model
 
 
 class EfficientViTSamPredictor:
