@@ -571,6 +571,47 @@ int omg_attn_relpos(int dtype, int B, int H, int W, int heads, int head_dim, int
                     const void* rel_h, const void* rel_w, const void* pad_kv, float scale, void* out, int64_t ldo, void* stream);
 int omg_gelu_erf(int dtype, const void* X, void* Y, int64_t n, void* stream);
 
+/* ------------------------------------------------------------------------
+ * The DPT-hybrid depth estimator (omg_amd/dpt.py: transformers' DPTForDepthEstimation for dpt-hybrid-midas, the network behind the
+ * "Depth" spatial condition) and the tail of the demos' get_depth.  Linear layers and 1x1 convolutions are omg_gemm, LayerNorms
+ * omg_layernorm, attention omg_attn_fwd, the MLP's activation omg_gelu_erf.  NHWC fp16 / bf16, fp32 accumulation and statistics,
+ * one rounding at the store; deterministic, and a sample's result does not depend on the batch it is in.
+ * TF-"SAME" padding at stride 2 (BiT): output size ceil(n / 2), total padding max((out - 1) 2 + k - n, 0), its smaller half in
+ *   front and the rest behind.
+ * omg_conv3x3_nhwc_ex: omg_conv3x3_nhwc_act's kernel with more of an epilogue.  act: 0 | 1 (tanh GELU) | 2 (ReLU).  flags bit 0: ReLU of
+ *   the INPUT as it is loaded (the residual, if any, is read as it is stored); bit 1: at stride 2 the SAME origin instead of padding 1
+ *   (padding in front: 0 for an even size, 1 for an odd one, per axis).  Output size (Hin - 1) / stride + 1 either way.
+ * omg_dpt_stem_conv: Y[B, ceil(H/2), ceil(W/2), Cout] NHWC = conv7x7 stride 2, SAME, of the NCHW pixel values X [B, 3, H, W] (in_dtype:
+ *   OMG_F32 or the storage dtype; rounded to the storage dtype as they are loaded).  Wp [Cout][148] in the storage dtype:
+ *   k = (ky 7 + kx) 3 + c, the last element zero.  No bias.  Cout % 32 == 0, Cout <= 128.
+ * omg_groupnorm_res_act: Y = relu?(GroupNorm(X) gamma + beta [+ residual]) over NHWC X [B, HW, C]; the statistics are omg_groupnorm's
+ *   (same kernels, same workspace: omg_groupnorm_ws_floats); residual [B, HW, C] may be NULL; relu 0 | 1.  Y may be X.
+ * omg_maxpool3x3s2_nhwc: 3x3 stride-2 max-pool under the SAME rule, padded with the VALUE 0 (which takes part in the maximum, as
+ *   BitMaxPool2d pads before it pools) -> [B, ceil(H/2), ceil(W/2), C].  C % 8 == 0.
+ * omg_upsample2x_bilinear_nhwc: Y [B, 2H, 2W, C] = bilinear resize, align_corners = True, as torch.nn.functional.interpolate computes
+ *   it in fp32.  C % 8 == 0.
+ * omg_rowdot_f32: Y[m] (fp32) = relu?(sum_c X[m][c] w[c] + bias[0]) for rows of ldx elements; w [C] and bias [1] (may be NULL) in the
+ *   storage dtype.  C % 8 == 0.  The 32 -> 1 projection of the depth head.
+ * omg_depth_tail: depth [B, h, w] fp32 -> out [B, H, W, 3] uint8:
+ *     r = bicubic resize (a = -0.75, align_corners = False, as torch.nn.functional.interpolate) of a sample to H x W, in fp32;
+ *     out = trunc(clip((r - min r) / (max r - min r) * 255, 0, 255)), the same byte three times.
+ *   Minimum and maximum are those of the RESIZED map (bicubic overshoots).  Two launches: per-block minima / maxima into the
+ *   workspace (omg_depth_tail_ws_floats floats), then a fold of them in every block and the resize again — r is never stored.
+ *   A constant map (where the reference divides zero by zero) gives zeros: max r - min r <= 2^-20 max(|min r|, |max r|), the rounding
+ *   noise the resize itself leaves on equal inputs, counts as no range.
+ * ---------------------------------------------------------------------- */
+int omg_conv3x3_nhwc_ex(int dtype, const void* X, int B, int Hin, int Win, int Cin, int Cout, int stride,
+                        const void* Wt, const void* bias, int act, const void* residual, int flags, void* Y, void* stream);
+int omg_dpt_stem_conv(int in_dtype, int dtype, const void* X, int B, int H, int W, int Cout, const void* Wp, void* Y, void* stream);
+int omg_groupnorm_res_act(int dtype, const void* X, int B, int HW, int C, int groups, float eps, const void* gamma, const void* beta,
+                          const void* residual, int relu, float* workspace, void* Y, void* stream);
+int omg_maxpool3x3s2_nhwc(int dtype, const void* X, int B, int H, int W, int C, void* Y, void* stream);
+int omg_upsample2x_bilinear_nhwc(int dtype, const void* X, int B, int H, int W, int C, void* Y, void* stream);
+int omg_rowdot_f32(int dtype, const void* X, int64_t ldx, int64_t M, int C, const void* w, const void* bias, int relu, float* Y,
+                   void* stream);
+int64_t omg_depth_tail_ws_floats(int B, int H, int W);
+int omg_depth_tail(const float* depth, int B, int h, int w, int H, int W, float* workspace, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,8 @@ _SAM = ("SamPromptEncoder", "SamMaskDecoder", "EfficientViTSam", "EfficientViTSa
         "efficientvit_sam_xl1", "create_sam_model", "set_norm_eps", "EfficientViTSamConfig", "EfficientViTSamImageEncoder")
 _SAM_VIT = ("SamImageEncoderViT",)
 _SEGMENT_ANYTHING = ("Sam", "SamPredictor", "ResizeLongestSide", "build_sam", "build_sam_vit_h", "build_sam_vit_l", "build_sam_vit_b", "sam_model_registry")
-__all__ = list(_SAM) + list(_SAM_VIT) + list(_SEGMENT_ANYTHING)
+_DPT = ("DPTForDepthEstimation", "DPTImageProcessor", "DPTFeatureExtractor", "depth_condition")
+__all__ = list(_SAM) + list(_SAM_VIT) + list(_SEGMENT_ANYTHING) + list(_DPT)
 
 
 def __getattr__(name):          # the segmenter's public names, imported on first use (omg_amd.sam pulls in torch and the kernels' bindings)
@@ -19,4 +20,7 @@ def __getattr__(name):          # the segmenter's public names, imported on firs
     if name in _SEGMENT_ANYTHING:
         from . import segment_anything
         return getattr(segment_anything, name)
+    if name in _DPT:
+        from . import dpt
+        return getattr(dpt, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

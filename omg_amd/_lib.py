@@ -179,6 +179,14 @@ SYMBOLS = {
     "omg_relu": (c_i32, [c_i32, c_vp, c_vp, c_i64, c_vp]),
     "omg_attn_relpos": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_f32, c_vp, c_i64, c_vp]),
     "omg_gelu_erf": (c_i32, [c_i32, c_vp, c_vp, c_i64, c_vp]),
+    "omg_conv3x3_nhwc_ex": (c_i32, [c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp]),
+    "omg_dpt_stem_conv": (c_i32, [c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "omg_groupnorm_res_act": (c_i32, [c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "omg_maxpool3x3s2_nhwc": (c_i32, [c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "omg_upsample2x_bilinear_nhwc": (c_i32, [c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "omg_rowdot_f32": (c_i32, [c_i32, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "omg_depth_tail_ws_floats": (c_i64, [c_i32, c_i32, c_i32]),
+    "omg_depth_tail": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "omg_debug_set_glds": (None, [c_i32]),
     "omg_debug_set_gemm_variant": (None, [c_i32]),
     "omg_debug_choose_variant": (c_i32, [c_i32, c_i32, c_i32, c_i32]),

@@ -32,7 +32,8 @@ constexpr int C3_ROWB = 80;
 
 template <typename T, int NT, bool VEC>
 __global__ __launch_bounds__(256) void conv3x3_kernel(const char* X, const char* Wt, const char* bias, const char* res, char* Y, int B,
-                                                      int Hin, int Win, int Cin, int Hout, int Wout, int Cout, int stride, int act) {
+                                                      int Hin, int Win, int Cin, int Hout, int Wout, int Cout, int stride, int act,
+                                                      int pad_t, int pad_l, int relu_in) {
   using v8 = typename Vec<T>::v8;
   constexpr int BN = 32 * NT;
   constexpr int WL = (BN * 4 + 255) / 256;                  // weight vectors per thread and chunk
@@ -58,8 +59,8 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(const char* X, const char*
       const int ox = (int)(m % Wout), oy = (int)((m / Wout) % Hout);
       const long b = m / ((long)Wout * Hout);
       xbase[i] = b * Hin * Win;
-      iy0[i] = oy * stride - 1;
-      ix0[i] = ox * stride - 1;
+      iy0[i] = oy * stride - pad_t;
+      ix0[i] = ox * stride - pad_l;
     } else {
       xbase[i] = 0;
       iy0[i] = -0x40000000;                                 // every tap lands outside the image: zeros
@@ -86,6 +87,10 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(const char* X, const char*
 #pragma unroll
           for (int c = 0; c < 8; ++c) e[c] = c < Cin ? ((const T*)X)[pix * Cin + c] : (T)0.0f;
           v = __builtin_bit_cast(u32x4, e);
+        }
+        if (relu_in) {                                      // max(x, 0) on the sign bits of the eight 16-bit values (fp16 and bf16 alike)
+#pragma unroll
+          for (int d = 0; d < 4; ++d) v[d] &= ~(((v[d] >> 15) & 0x00010001u) * 0xffffu);
         }
       }
       rx[i] = v;
@@ -160,9 +165,12 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(const char* X, const char*
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] += (float)bv[e];
       }
-      if (act) {
+      if (act == 1) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = gelu_tanh_f(v[e]);
+      } else if (act == 2) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = v[e] < 0.f ? 0.f : v[e];
       }
       if (res != nullptr) {
         const typename Vec<T>::v4 rv = *(const typename Vec<T>::v4*)(res + (m * Cout + c) * (long)sizeof(T));
@@ -178,12 +186,12 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(const char* X, const char*
 
 template <typename T>
 int conv3x3_launch(const void* X, const void* Wt, const void* bias, const void* res, void* Y, int B, int Hin, int Win, int Cin, int Hout,
-                   int Wout, int Cout, int stride, int act, hipStream_t s) {
+                   int Wout, int Cout, int stride, int act, int pad_t, int pad_l, int relu_in, hipStream_t s) {
   const long M = (long)B * Hout * Wout;
   const unsigned gx = (unsigned)((M + C3_BM - 1) / C3_BM);
 #define OMG_C3(NT_, VEC_)                                                                                                              \
   OMG_LAUNCH((conv3x3_kernel<T, NT_, VEC_>), dim3(gx, (unsigned)((Cout + 32 * NT_ - 1) / (32 * NT_))), dim3(256), 0, s, (const char*)X, \
-             (const char*)Wt, (const char*)bias, (const char*)res, (char*)Y, B, Hin, Win, Cin, Hout, Wout, Cout, stride, act)
+             (const char*)Wt, (const char*)bias, (const char*)res, (char*)Y, B, Hin, Win, Cin, Hout, Wout, Cout, stride, act, pad_t, pad_l, relu_in)
   const bool vec = Cin % 8 == 0;
   if (Cout <= 32) { if (vec) OMG_C3(1, true); else OMG_C3(1, false); }
   else if (Cout <= 64) { if (vec) OMG_C3(2, true); else OMG_C3(2, false); }
@@ -313,8 +321,35 @@ extern "C" int omg_conv3x3_nhwc_act(int dtype, const void* X, int B, int Hin, in
   if (M == 0) return OMG_OK;
   OMG_REQUIRE((M + C3_BM - 1) / C3_BM <= 0x7fffffffL && (Cout + 31) / 32 <= 65535, "omg_conv3x3_nhwc_act: grid limits");
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == OMG_F16) return conv3x3_launch<f16>(X, Wt, bias, residual, Y, B, Hin, Win, Cin, Hout, Wout, Cout, stride, act, s);
-  return conv3x3_launch<bf16>(X, Wt, bias, residual, Y, B, Hin, Win, Cin, Hout, Wout, Cout, stride, act, s);
+  if (dtype == OMG_F16) return conv3x3_launch<f16>(X, Wt, bias, residual, Y, B, Hin, Win, Cin, Hout, Wout, Cout, stride, act, 1, 1, 0, s);
+  return conv3x3_launch<bf16>(X, Wt, bias, residual, Y, B, Hin, Win, Cin, Hout, Wout, Cout, stride, act, 1, 1, 0, s);
+}
+
+// The same kernel with what the DPT depth estimator (omg_amd/dpt.py) needs of it: a ReLU epilogue, ReLU of the input as it is loaded
+// (the pre-activation residual unit reads x and relu(x)), and the origin of TF-"SAME" padding at stride 2: total padding
+// (Hout - 1) 2 + 3 - Hin with Hout = ceil(Hin / 2), its smaller half in front — 0 in front of an even size, 1 in front of an odd one.
+extern "C" int omg_conv3x3_nhwc_ex(int dtype, const void* X, int B, int Hin, int Win, int Cin, int Cout, int stride, const void* Wt,
+                                   const void* bias, int act, const void* residual, int flags, void* Y, void* stream) {
+  OMG_REQUIRE(dtype == OMG_F16 || dtype == OMG_BF16, "omg_conv3x3_nhwc_ex: dtype");
+  OMG_REQUIRE(X && Wt && Y, "omg_conv3x3_nhwc_ex: null operand");
+  OMG_REQUIRE(stride == 1 || stride == 2, "omg_conv3x3_nhwc_ex: stride 1 or 2");
+  OMG_REQUIRE(B >= 0 && Hin > 0 && Win > 0, "omg_conv3x3_nhwc_ex: shape");
+  OMG_REQUIRE(Cin > 0 && (Cin % 8 == 0 || Cin < 8), "omg_conv3x3_nhwc_ex: Cin a multiple of 8, or below 8");
+  OMG_REQUIRE(Cout > 0 && Cout % 8 == 0, "omg_conv3x3_nhwc_ex: Cout a multiple of 8");
+  OMG_REQUIRE(act >= 0 && act <= 2, "omg_conv3x3_nhwc_ex: act 0 (none), 1 (tanh GELU) or 2 (ReLU)");
+  OMG_REQUIRE((flags & ~3) == 0, "omg_conv3x3_nhwc_ex: flags bit 0 (ReLU of the input) | bit 1 (SAME origin)");
+  OMG_REQUIRE((long)9 * ((Cin + 7) / 8 * 8) < (1 << 24), "omg_conv3x3_nhwc_ex: Cin");
+  OMG_REQUIRE(Cin % 8 != 0 || ((uintptr_t)X % 16 == 0 && (uintptr_t)Wt % 16 == 0), "omg_conv3x3_nhwc_ex: 16-byte aligned X, W");
+  OMG_REQUIRE((uintptr_t)Y % 8 == 0 && (uintptr_t)bias % 8 == 0 && (uintptr_t)residual % 8 == 0, "omg_conv3x3_nhwc_ex: 8-byte aligned Y, bias, residual");
+  const int Hout = (Hin - 1) / stride + 1, Wout = (Win - 1) / stride + 1;      // = ceil(Hin / stride): the SAME rule's size too
+  const bool same = (flags & 2) != 0 && stride == 2;
+  const int pad_t = same ? (Hin & 1) : 1, pad_l = same ? (Win & 1) : 1;
+  const long M = (long)B * Hout * Wout;
+  if (M == 0) return OMG_OK;
+  OMG_REQUIRE((M + C3_BM - 1) / C3_BM <= 0x7fffffffL && (Cout + 31) / 32 <= 65535, "omg_conv3x3_nhwc_ex: grid limits");
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == OMG_F16) return conv3x3_launch<f16>(X, Wt, bias, residual, Y, B, Hin, Win, Cin, Hout, Wout, Cout, stride, act, pad_t, pad_l, flags & 1, s);
+  return conv3x3_launch<bf16>(X, Wt, bias, residual, Y, B, Hin, Win, Cin, Hout, Wout, Cout, stride, act, pad_t, pad_l, flags & 1, s);
 }
 
 extern "C" int omg_dwconv3x3_act(int dtype, const void* X, int64_t ldx, int B, int Hin, int Win, int C, int stride, const void* Wt,

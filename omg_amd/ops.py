@@ -895,6 +895,127 @@ def gelu_erf(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tenso
     return out
 
 
+def conv3x3_nhwc_ex(x: torch.Tensor, w: torch.Tensor, *, stride: int = 1, bias: Optional[torch.Tensor] = None, act: int = 0,
+                    residual: Optional[torch.Tensor] = None, relu_in: bool = False, same: bool = False,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`conv3x3_nhwc_act`'s kernel with ``act`` 0 | 1 (tanh GELU) | 2 (ReLU), ReLU of the input as it is loaded (``relu_in``; the
+    residual is read as stored) and, at stride 2, TF-"SAME" padding (``same``: nothing in front of an even size).  omg_conv3x3_nhwc_ex."""
+    _dev(x)
+    B, H, W, Cin = x.shape
+    Cout = w.shape[0]
+    assert x.is_contiguous() and w.is_contiguous() and w.shape == (Cout, 3, 3, Cin) and w.dtype == x.dtype
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    if out is None:
+        out = torch.empty((B, Ho, Wo, Cout), dtype=x.dtype, device=x.device)
+    assert out.shape == (B, Ho, Wo, Cout) and out.is_contiguous() and out.dtype == x.dtype
+    if residual is not None:
+        assert residual.shape == out.shape and residual.is_contiguous() and residual.dtype == x.dtype
+    t0 = _PROF.begin() if _PROF is not None else None
+    L.check(L.lib().omg_conv3x3_nhwc_ex(_dt(x), x.data_ptr(), B, H, W, Cin, Cout, stride, w.data_ptr(), _p(bias), int(act), _p(residual),
+                                        int(relu_in) | (int(same) << 1), out.data_ptr(), _stream()), "omg_conv3x3_nhwc_ex")
+    if _PROF is not None:
+        _PROF.end("conv3x3_nhwc", 2.0 * B * Ho * Wo * Cout * 9 * Cin, t0, ("conv3x3_nhwc", B * Ho * Wo, Cout, 9 * Cin, stride))
+    return out
+
+
+def _out(out: Optional[torch.Tensor], shape, dtype, device) -> torch.Tensor:
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    assert tuple(out.shape) == tuple(shape) and out.is_contiguous() and out.dtype == dtype and out.device == device
+    return out
+
+
+def pack_dpt_stem_weight(w_oihw: torch.Tensor) -> torch.Tensor:
+    """[Cout, 3, 7, 7] -> [Cout, 148]: k = (ky * 7 + kx) * 3 + c, one zero behind (74 pairs for the packed dot products)."""
+    cout = w_oihw.shape[0]
+    assert w_oihw.shape[1:] == (3, 7, 7)
+    out = torch.zeros((cout, 148), dtype=w_oihw.dtype, device=w_oihw.device)
+    out[:, :147] = w_oihw.permute(0, 2, 3, 1).reshape(cout, 147)
+    return out
+
+
+def dpt_stem_conv(x_nchw: torch.Tensor, w_packed: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """BiT's stem: 7x7 stride-2 convolution, TF-"SAME" padding, of NCHW pixel values (fp32 or the weights' dtype) -> NHWC
+    [B, ceil(H/2), ceil(W/2), Cout] in the weights' dtype.  ``w_packed`` from :func:`pack_dpt_stem_weight`.  omg_dpt_stem_conv."""
+    _dev(x_nchw)
+    B, Cin, H, W = x_nchw.shape
+    Cout = w_packed.shape[0]
+    assert Cin == 3 and x_nchw.is_contiguous() and w_packed.shape == (Cout, 148) and w_packed.is_contiguous()
+    assert x_nchw.dtype in (torch.float32, w_packed.dtype)
+    y = _out(out, (B, (H + 1) // 2, (W + 1) // 2, Cout), w_packed.dtype, x_nchw.device)
+    L.check(L.lib().omg_dpt_stem_conv(_dt(x_nchw, allow_f32=True), _dt(w_packed), x_nchw.data_ptr(), B, H, W, Cout, w_packed.data_ptr(),
+                                      y.data_ptr(), _stream()), "omg_dpt_stem_conv")
+    return y
+
+
+def groupnorm_res_act(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups: int, eps: float, *,
+                      residual: Optional[torch.Tensor] = None, relu: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``relu?(GroupNorm(x) * gamma + beta [+ residual])`` of NHWC ``x`` (B, H, W, C) or (B, HW, C): :func:`groupnorm`'s statistics,
+    the residual add and the ReLU in the apply pass.  omg_groupnorm_res_act."""
+    _dev(x)
+    assert x.is_contiguous() and gamma.dtype == x.dtype and beta.dtype == x.dtype
+    B, Cc = x.shape[0], x.shape[-1]
+    HW = x.numel() // max(B * Cc, 1)
+    if residual is not None:
+        assert residual.shape == x.shape and residual.is_contiguous() and residual.dtype == x.dtype
+    y = _out(out, tuple(x.shape), x.dtype, x.device)
+    ws = _gn_workspace(x.device, B, groups, HW)
+    L.check(L.lib().omg_groupnorm_res_act(_dt(x), x.data_ptr(), B, HW, Cc, groups, eps, gamma.data_ptr(), beta.data_ptr(), _p(residual),
+                                          int(relu), ws.data_ptr(), y.data_ptr(), _stream()), "omg_groupnorm_res_act")
+    return y
+
+
+def maxpool3x3s2_nhwc(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """3x3 stride-2 max-pool of NHWC ``x`` under TF-"SAME" padding with pad value 0 -> [B, ceil(H/2), ceil(W/2), C].  omg_maxpool3x3s2_nhwc."""
+    _dev(x)
+    B, H, W, Cc = x.shape
+    assert x.is_contiguous()
+    y = _out(out, (B, (H + 1) // 2, (W + 1) // 2, Cc), x.dtype, x.device)
+    L.check(L.lib().omg_maxpool3x3s2_nhwc(_dt(x), x.data_ptr(), B, H, W, Cc, y.data_ptr(), _stream()), "omg_maxpool3x3s2_nhwc")
+    return y
+
+
+def upsample2x_bilinear_nhwc(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Bilinear x2 resize (align_corners=True) of NHWC ``x`` -> [B, 2H, 2W, C].  omg_upsample2x_bilinear_nhwc."""
+    _dev(x)
+    B, H, W, Cc = x.shape
+    assert x.is_contiguous()
+    y = _out(out, (B, 2 * H, 2 * W, Cc), x.dtype, x.device)
+    L.check(L.lib().omg_upsample2x_bilinear_nhwc(_dt(x), x.data_ptr(), B, H, W, Cc, y.data_ptr(), _stream()), "omg_upsample2x_bilinear_nhwc")
+    return y
+
+
+def rowdot_f32(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, relu: bool = False,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``relu?(x @ w + bias)`` in fp32 for rows ``x`` [M, C] (unit inner stride), ``w`` [C], ``bias`` [1] -> fp32 [M].  omg_rowdot_f32."""
+    _dev(x)
+    M, Cc = x.shape
+    assert x.stride(1) == 1 and w.shape == (Cc,) and w.is_contiguous() and w.dtype == x.dtype
+    if bias is not None:
+        assert bias.numel() == 1 and bias.dtype == x.dtype
+    y = _out(out, (M,), torch.float32, x.device)
+    L.check(L.lib().omg_rowdot_f32(_dt(x), x.data_ptr(), x.stride(0), M, Cc, w.data_ptr(), _p(bias), int(relu), y.data_ptr(), _stream()), "omg_rowdot_f32")
+    return y
+
+
+def depth_tail(depth: torch.Tensor, size: Tuple[int, int], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The tail of the demos' ``get_depth``: fp32 ``depth`` [B, h, w] -> uint8 [B, H, W, 3]: bicubic resize (align_corners=False) to
+    ``size``, min-max normalisation of the resized map per sample, x 255, clipped and truncated, three equal channels.  A constant map
+    gives zeros.  omg_depth_tail."""
+    _dev(depth)
+    if depth.dtype != torch.float32 or depth.dim() != 3:
+        raise L.OmgHipError(f"depth_tail takes a float32 [B, h, w] map, not {depth.dtype} {tuple(depth.shape)}")
+    B, h, w = depth.shape
+    H, W = int(size[0]), int(size[1])
+    assert depth.is_contiguous()
+    if out is None:
+        out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=depth.device)
+    assert out.shape == (B, H, W, 3) and out.is_contiguous() and out.dtype == torch.uint8
+    ws = torch.empty((max(int(L.lib().omg_depth_tail_ws_floats(B, H, W)), 1),), dtype=torch.float32, device=depth.device)      # per call: see _gn_workspace
+    L.check(L.lib().omg_depth_tail(depth.data_ptr(), B, h, w, H, W, ws.data_ptr(), out.data_ptr(), _stream()), "omg_depth_tail")
+    return out
+
+
 def conv_in(x_nchw: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], dtype: torch.dtype) -> torch.Tensor:
     """NCHW latents (fp32 or `dtype`) -> NHWC features in `dtype`; w: [Cout][64] from pack_conv_in_weight."""
     _dev(x_nchw)
