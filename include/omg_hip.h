@@ -612,6 +612,38 @@ int omg_rowdot_f32(int dtype, const void* X, int64_t ldx, int64_t M, int C, cons
 int64_t omg_depth_tail_ws_floats(int B, int H, int W);
 int omg_depth_tail(const float* depth, int B, int h, int w, int H, int W, float* workspace, void* out, void* stream);
 
+/* ------------------------------------------------------------------------
+ * The Swin backbone (omg_amd/swin.py: transformers' SwinBackbone, the image backbone of GroundingDINO).  Linear layers are omg_gemm,
+ * LayerNorms omg_layernorm, the MLP's activation omg_gelu_erf.
+ * omg_attn_swin: (shifted-)window softmax attention per head, head_dim 32, read straight from the fused QKV projection.  qkv
+ *   [B H W][ld]: rows in image order, columns q | k | v, each heads * 32 wide and head-major; out [B H W][ldo], head-major; ld, ldo
+ *   multiples of 8, base pointers 16-byte aligned.  window S = 7 | 12, shift 0 | S / 2, any heads >= 1, any H, W >= 1 (grids smaller
+ *   than the window included: the window is never clamped, as SwinBackbone runs its encoder with always_partition).
+ *   The grid is padded at the bottom and right to (Hp, Wp), multiples of S, rolled by -shift on both axes, and cut into S x S windows
+ *   from the top left; none of that is materialised: position (ry, rx) of the rolled grid is position ((ry + shift) mod Hp,
+ *   (rx + shift) mod Wp) of the padded one.  A query attends to the S S positions of its window:
+ *     score(q, k) = scale q.k + table[(qiy - kiy + S - 1) (2 S - 1) + (qix - kix + S - 1)][head]  (+ -100 if region(q) != region(k))
+ *   with (iy, ix) the position inside the window; table [(2 S - 1)^2][heads] is the checkpoint's relative_position_bias_table in the
+ *   storage dtype.  region (shift > 0 only) = 3 band(ry, Hp) + band(rx, Wp), band(c, n) = [0, n - S) | [n - S, n - shift) |
+ *   [n - shift, n): the additive mask of SwinLayer.get_attn_mask, not an exclusion.
+ *   A position beyond the H x W grid is a real key, shifted or not, with k | v = pad_kv [2 heads 32] (null: zeros) — what zero
+ *   padding after the norm gives: the k and v slices of the QKV bias.  Queries beyond the grid are not computed, their rows not
+ *   written; out columns beyond heads * 32 are not written.  The keys that only pad 49 to the MFMA tile are excluded exactly.
+ *   Scores, bias, mask, softmax and P V are fp32 (16-bit MFMA operands); a window's softmax is one pass over registers.  The
+ *   reduction order inside a (window, head) is fixed: results do not depend on the batch or on other windows.
+ * omg_swin_patch_embed: Y [B ceil(H/4) ceil(W/4)][ldy] = the 4 x 4 stride-4 patches of the NCHW pixel values X [B, 3, H, W] (in_dtype:
+ *   OMG_F32 or the storage dtype), zero beyond the image; column k = (c 4 + ky) 4 + kx, the order of projection.weight.reshape(C, 48);
+ *   columns 48 .. ldy - 1 are written as zeros.  ldy % 8 == 0, ldy >= 48.
+ * omg_swin_merge_ln: Y [B ceil(H/2) ceil(W/2)][4 C] = LayerNorm over 4 C (fp32 statistics, two passes over registers) of the 2 x 2
+ *   neighbourhoods of X [B, H, W, C], channel blocks (dy, dx) = (0,0), (1,0), (0,1), (1,1); a position beyond an odd H or W is zeros
+ *   BEFORE the norm.  gamma, beta [4 C].  C % 8 == 0, C <= 1024.
+ * ---------------------------------------------------------------------- */
+int omg_attn_swin(int dtype, int B, int H, int W, int heads, int window, int shift, const void* qkv, int64_t ld,
+                  const void* table, const void* pad_kv, float scale, void* out, int64_t ldo, void* stream);
+int omg_swin_patch_embed(int in_dtype, int dtype, const void* X, int B, int H, int W, void* Y, int64_t ldy, void* stream);
+int omg_swin_merge_ln(int dtype, const void* X, int B, int H, int W, int C, const void* gamma, const void* beta, float eps,
+                      void* Y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -187,6 +187,9 @@ SYMBOLS = {
     "omg_rowdot_f32": (c_i32, [c_i32, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "omg_depth_tail_ws_floats": (c_i64, [c_i32, c_i32, c_i32]),
     "omg_depth_tail": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "omg_attn_swin": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_f32, c_vp, c_i64, c_vp]),
+    "omg_swin_patch_embed": (c_i32, [c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp]),
+    "omg_swin_merge_ln": (c_i32, [c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp]),
     "omg_debug_set_glds": (None, [c_i32]),
     "omg_debug_set_gemm_variant": (None, [c_i32]),
     "omg_debug_choose_variant": (c_i32, [c_i32, c_i32, c_i32, c_i32]),

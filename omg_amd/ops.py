@@ -895,6 +895,55 @@ def gelu_erf(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tenso
     return out
 
 
+def attn_swin(qkv: torch.Tensor, B: int, H: int, W: int, heads: int, table: torch.Tensor, scale: float, *, window: int, shift: int = 0,
+              pad_kv: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Swin's (shifted-)window attention on the fused projection ``qkv`` [B*H*W, 3*heads*32] (rows in image order, columns q | k | v,
+    head-major; any row stride that is a multiple of 8) -> [B*H*W, heads*32].  ``window`` S = 7 | 12, ``shift`` 0 | S // 2; ``table``
+    [(2S-1)^2, heads] is the checkpoint's relative_position_bias_table; positions beyond the grid are keys with k | v = ``pad_kv``
+    [2*heads*32] (None: zeros).  Pad, roll, partition, bias, mask and reverse happen inside the kernel.  omg_attn_swin."""
+    _dev(qkv)
+    M, Wd = qkv.shape
+    d = 32
+    assert M == B * H * W and Wd == 3 * heads * d and qkv.stride(1) == 1
+    if tuple(table.shape) != ((2 * window - 1) ** 2, heads):
+        raise L.OmgHipError(f"attn_swin: the bias table is {tuple(table.shape)}, window {window} with {heads} heads needs "
+                            f"({(2 * window - 1) ** 2}, {heads}) (no interpolation of the table)")
+    assert table.is_contiguous() and table.dtype == qkv.dtype and table.is_cuda
+    if pad_kv is not None:
+        assert pad_kv.shape == (2 * heads * d,) and pad_kv.is_contiguous() and pad_kv.dtype == qkv.dtype and pad_kv.is_cuda
+    if out is None:
+        out = torch.empty((M, heads * d), dtype=qkv.dtype, device=qkv.device)
+    assert out.shape[0] == M and out.shape[1] >= heads * d and out.stride(1) == 1 and out.dtype == qkv.dtype
+    L.check(L.lib().omg_attn_swin(_dt(qkv), B, H, W, heads, window, shift, qkv.data_ptr(), qkv.stride(0), table.data_ptr(), _p(pad_kv),
+                                  scale, out.data_ptr(), out.stride(0), _stream()), "omg_attn_swin")
+    return out
+
+
+def swin_patch_embed(x_nchw: torch.Tensor, dtype: torch.dtype, ld: int = 64, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """NCHW pixel values [B, 3, H, W] (fp32 or ``dtype``) -> the 4x4 stride-4 patch rows [B*ceil(H/4)*ceil(W/4), ld] in ``dtype``:
+    column k = (c*4 + ky)*4 + kx, zeros beyond the image and in columns 48 .. ld-1.  omg_swin_patch_embed."""
+    _dev(x_nchw)
+    B, Cin, H, W = x_nchw.shape
+    assert Cin == 3 and x_nchw.is_contiguous() and x_nchw.dtype in (torch.float32, dtype)
+    y = _out(out, (B * ((H + 3) // 4) * ((W + 3) // 4), ld), dtype, x_nchw.device)
+    L.check(L.lib().omg_swin_patch_embed(_dt(x_nchw, allow_f32=True), _DT[dtype], x_nchw.data_ptr(), B, H, W, y.data_ptr(), ld, _stream()),
+            "omg_swin_patch_embed")
+    return y
+
+
+def swin_merge_ln(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Patch merging's gather and LayerNorm: NHWC ``x`` [B, H, W, C] -> [B*ceil(H/2)*ceil(W/2), 4C], channel blocks (0,0), (1,0), (0,1),
+    (1,1), an odd H or W zero-padded before the norm.  omg_swin_merge_ln."""
+    _dev(x)
+    B, H, W, Cc = x.shape
+    assert x.is_contiguous() and gamma.shape == (4 * Cc,) and beta.shape == (4 * Cc,) and gamma.dtype == x.dtype and beta.dtype == x.dtype
+    assert gamma.is_contiguous() and beta.is_contiguous()
+    y = _out(out, (B * ((H + 1) // 2) * ((W + 1) // 2), 4 * Cc), x.dtype, x.device)
+    L.check(L.lib().omg_swin_merge_ln(_dt(x), x.data_ptr(), B, H, W, Cc, gamma.data_ptr(), beta.data_ptr(), eps, y.data_ptr(), _stream()),
+            "omg_swin_merge_ln")
+    return y
+
+
 def conv3x3_nhwc_ex(x: torch.Tensor, w: torch.Tensor, *, stride: int = 1, bias: Optional[torch.Tensor] = None, act: int = 0,
                     residual: Optional[torch.Tensor] = None, relu_in: bool = False, same: bool = False,
                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
