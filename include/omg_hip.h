@@ -488,6 +488,10 @@ int omg_attn_apply_probs(int dtype, const void* P, const void* V, int64_t ldv, i
  *   rounded once to the storage dtype) and the 1x1 convolution with C / dim groups behind it on the 16-bit MFMA (fp32 accumulation,
  *   one rounding).  Wg [C][dim] is the grouped convolution's own weight.  dim in {16, 32}, C a multiple of dim.  Y may be another
  *   column slice of the buffer X is a slice of (ldx == ldy, disjoint columns); any other overlap is refused.
+ * omg_dwconv2d and omg_relu_linear_att refuse a negative B, H, W or HW and return OMG_OK without a launch when B, H, W or HW is 0.
+ *   Both do 16-byte accesses: X, the taps, bias (when given), Y, QKV and OUT must be 16-byte aligned (with ldx, ldy, ld, ldo
+ *   multiples of 8 elements every row then is); the workspace holds floats.  omg_relu_linear_att writes every float of
+ *   workspace[0 .. omg_relu_linear_att_ws_floats) before it reads it and touches none behind.
  * ---------------------------------------------------------------------- */
 int omg_dwconv2d(int dtype, const void* X, int64_t ldx, int B, int H, int W, int C, int ksize,
                  const void* Wt, const void* bias, void* Y, int64_t ldy, void* stream);

@@ -216,6 +216,8 @@ extern "C" int omg_dwconv2d(int dtype, const void* X, int64_t ldx, int B, int H,
   OMG_REQUIRE(X && Wt && Y, "omg_dwconv2d: null operand");
   OMG_REQUIRE(C > 0 && C % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0 && ldx >= C && ldy >= C, "omg_dwconv2d: C, ldx, ldy multiples of 8");
   OMG_REQUIRE(ksize >= 1 && ksize <= 9 && (ksize & 1), "omg_dwconv2d: odd kernel size <= 9");
+  OMG_REQUIRE(B >= 0 && H >= 0 && W >= 0, "omg_dwconv2d: shape");
+  OMG_REQUIRE((uintptr_t)X % 16 == 0 && (uintptr_t)Wt % 16 == 0 && (uintptr_t)bias % 16 == 0 && (uintptr_t)Y % 16 == 0, "omg_dwconv2d: 16-byte aligned X, taps, bias, Y");
   const long total = (long)B * H * W * (C / 8);
   if (total == 0) return OMG_OK;
   hipStream_t s = (hipStream_t)stream;
@@ -265,7 +267,9 @@ extern "C" int omg_relu_linear_att(int dtype, const void* QKV, int64_t ld, int B
   OMG_REQUIRE(QKV && workspace && OUT, "omg_relu_linear_att: null operand");
   OMG_REQUIRE(dim == 8 || dim == 16 || dim == 32, "omg_relu_linear_att: dim must be 8, 16 or 32");
   OMG_REQUIRE(ld % 8 == 0 && ldo % 8 == 0 && ld >= (int64_t)groups * 3 * dim && ldo >= (int64_t)groups * dim, "omg_relu_linear_att: ld, ldo");
+  OMG_REQUIRE(B >= 0 && HW >= 0, "omg_relu_linear_att: shape");
   OMG_REQUIRE(groups > 0 && groups <= 65535 && B <= 65535, "omg_relu_linear_att: grid limits");
+  OMG_REQUIRE((uintptr_t)QKV % 16 == 0 && (uintptr_t)OUT % 16 == 0 && (uintptr_t)workspace % 4 == 0, "omg_relu_linear_att: 16-byte aligned QKV, OUT; 4-byte aligned workspace");
   if (B == 0 || HW == 0) return OMG_OK;
   hipStream_t s = (hipStream_t)stream;
 #define RLA(TT, DD) return rla_launch<TT, DD>(QKV, (long)ld, B, HW, groups, eps, workspace, OUT, (long)ldo, s)

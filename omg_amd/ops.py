@@ -664,13 +664,27 @@ def layernorm_mx8(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps:
     return out
 
 
-def dwconv2d(x: torch.Tensor, taps: torch.Tensor, B: int, H: int, W: int, ksize: int, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+def dwconv2d(x: torch.Tensor, taps: torch.Tensor, B: int, H: int, W: int, ksize: int, bias: Optional[torch.Tensor] = None,
+             out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Depthwise ``ksize x ksize`` convolution (stride 1, same padding) of NHWC rows ``x`` [B*H*W, C] (any row stride: a column slice
-    of a wider buffer is fine); ``taps`` [ksize*ksize, C] tap-major.  omg_dwconv2d — LiteMLA's multi-scale aggregation."""
+    of a wider buffer is fine); ``taps`` [ksize*ksize, C] tap-major; ``out`` [B*H*W, C] with any row stride, not overlapping ``x``.
+    omg_dwconv2d — LiteMLA's multi-scale aggregation."""
     _dev(x)
     M, Cc = x.shape
-    assert M == B * H * W and x.stride(1) == 1 and taps.shape == (ksize * ksize, Cc) and taps.is_contiguous()
-    y = torch.empty((M, Cc), dtype=x.dtype, device=x.device)
+    assert M == B * H * W and x.stride(1) == 1 and taps.shape == (ksize * ksize, Cc) and taps.is_contiguous() and taps.dtype == x.dtype
+    if bias is not None:
+        assert bias.shape == (Cc,) and bias.is_contiguous() and bias.dtype == x.dtype and bias.device == x.device
+    if out is None:
+        y = torch.empty((M, Cc), dtype=x.dtype, device=x.device)
+    else:
+        y = out
+        assert y.shape == (M, Cc) and y.stride(1) == 1 and y.dtype == x.dtype and y.device == x.device
+        es = x.element_size()
+        x0, y0 = x.data_ptr(), y.data_ptr()
+        if M and x0 < y0 + ((M - 1) * y.stride(0) + Cc) * es and y0 < x0 + ((M - 1) * x.stride(0) + Cc) * es:
+            # the same buffer: the same rows, and columns that x does not have
+            dcol = abs(y0 - x0) // es % max(x.stride(0), 1)
+            assert x.stride(0) == y.stride(0) and Cc <= dcol <= x.stride(0) - Cc, "dwconv2d: out overlaps x"
     t0 = _PROF.begin() if _PROF is not None else None
     L.check(L.lib().omg_dwconv2d(_dt(x), x.data_ptr(), x.stride(0), B, H, W, Cc, ksize, taps.data_ptr(), _p(bias), y.data_ptr(), y.stride(0), _stream()),
             "omg_dwconv2d")
@@ -706,14 +720,29 @@ def litemla_aggreg(x: torch.Tensor, taps: torch.Tensor, wg: torch.Tensor, B: int
     return out
 
 
-def relu_linear_att(qkv: torch.Tensor, B: int, HW: int, groups: int, dim: int, eps: float) -> torch.Tensor:
+def relu_linear_att(qkv: torch.Tensor, B: int, HW: int, groups: int, dim: int, eps: float, out: Optional[torch.Tensor] = None,
+                    workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """EfficientViT's ReLU linear attention (fp32 inside) on NHWC rows ``qkv`` [B*HW, groups*3*dim] (group g: q | k | v at columns
-    3 dim g) -> [B*HW, groups*dim].  omg_relu_linear_att."""
+    3 dim g; any row stride) -> [B*HW, groups*dim].  ``out`` may have any row stride and must not overlap ``qkv``; ``workspace`` is a
+    contiguous fp32 tensor of at least omg_relu_linear_att_ws_floats elements, every one of which the call writes before it reads it.
+    omg_relu_linear_att."""
     _dev(qkv)
     M, Cc = qkv.shape
     assert M == B * HW and Cc == groups * 3 * dim and qkv.stride(1) == 1
-    out = torch.empty((M, groups * dim), dtype=qkv.dtype, device=qkv.device)
-    ws = torch.empty((int(L.lib().omg_relu_linear_att_ws_floats(B, groups, dim, HW)),), dtype=torch.float32, device=qkv.device)
+    if out is None:
+        out = torch.empty((M, groups * dim), dtype=qkv.dtype, device=qkv.device)
+    else:
+        assert out.shape == (M, groups * dim) and out.stride(1) == 1 and out.dtype == qkv.dtype and out.device == qkv.device
+        es = qkv.element_size()
+        x0, y0 = qkv.data_ptr(), out.data_ptr()
+        assert not (M and x0 < y0 + ((M - 1) * out.stride(0) + groups * dim) * es and y0 < x0 + ((M - 1) * qkv.stride(0) + Cc) * es), \
+            "relu_linear_att: out overlaps qkv"
+    need = int(L.lib().omg_relu_linear_att_ws_floats(B, groups, dim, HW))
+    if workspace is None:
+        ws = torch.empty((need,), dtype=torch.float32, device=qkv.device)
+    else:
+        ws = workspace
+        assert ws.dtype == torch.float32 and ws.device == qkv.device and ws.dim() == 1 and ws.is_contiguous() and ws.numel() >= need
     t0 = _PROF.begin() if _PROF is not None else None
     L.check(L.lib().omg_relu_linear_att(_dt(qkv), qkv.data_ptr(), qkv.stride(0), B, HW, groups, dim, eps, ws.data_ptr(), out.data_ptr(), out.stride(0),
                                         _stream()), "omg_relu_linear_att")
