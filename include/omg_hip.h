@@ -648,6 +648,74 @@ int omg_swin_patch_embed(int in_dtype, int dtype, const void* X, int B, int H, i
 int omg_swin_merge_ln(int dtype, const void* X, int B, int H, int W, int C, const void* gamma, const void* beta, float eps,
                       void* Y, void* stream);
 
+/* ------------------------------------------------------------------------
+ * GroundingDINO's feature enhancer (omg_amd/gdino.py: transformers' GroundingDinoEncoder and the neck in front of it).  Linear layers
+ * and the neck's 1x1 convolutions are omg_gemm, LayerNorms omg_layernorm, the neck's GroupNorm omg_groupnorm_res_act, the extra
+ * level omg_conv3x3_nhwc_act at stride 2, the MLPs' activation omg_relu.  Storage fp16 / bf16, arithmetic fp32, one rounding at the
+ * store; no atomics; every reduction order is fixed by the sample's own sizes, so a sample's result does not depend on the batch it is
+ * in and a graph replay equals the eager call.  Byte masks: 1 (non-zero) = valid / attend, 0 = padded / excluded, everywhere.
+ *
+ * omg_msdeform_attn: what GroundingDinoMultiscaleDeformableAttention.forward does between its Linear layers.
+ *   value [B N][ldv]: the rows of value_proj, head-major, heads x 32; mask [B N] or NULL: a row whose byte is 0 reads as zeros (the
+ *     library's masked_fill of the value, NOT a score mask).
+ *   ow [B Nq][ldow]: the fused rows of sampling_offsets | attention_weights: heads L 4 2 offsets ordered (head, level, point, xy), then
+ *     heads L 4 logits ordered (head, level point).  ref [B Nq L 2] fp32, (x, y) in [0, 1] units of each sampled level.
+ *   H[l], W[l], start[l]: level l is rows start[l] .. start[l] + H[l] W[l] - 1 of a sample, row-major.
+ *   Per (query, head): a = softmax over the L 4 logits; loc = ref + off / (W_l, H_l); pixel x = loc_x W_l - 0.5 (computed as
+ *     ref_x W_l + off_x - 0.5), y alike: bilinear, align_corners = False, a corner outside the level contributes 0;
+ *     out [B Nq][ldo] (head-major) = sum over level, point, corner of a w_corner value, in that order, fp32.
+ *   head_dim 32, points 4, 1 <= L <= 4: anything else is refused.  Row strides multiples of 8, base pointers 16-byte aligned.  Value
+ *     rows are taken to be finite (a corner of weight 0 is still read, from a clamped address).  out columns beyond heads 32 are not
+ *     written.  B or Nq == 0: nothing to do.
+ *
+ * omg_attn_bi_vision / omg_attn_bi_text: the two halves of GroundingDinoBiMultiHeadAttention, head_dim 256, read from the fused
+ *   projection rows vis [B N][ld_vis] = vision q | vision v and txt [B T][ld_txt] = text k | text v (each heads 256 wide, head-major;
+ *   samples vis_bstride / txt_bstride elements apart).  T <= 256.  scale is the library's `scale` on q, applied to the fp32 score in
+ *   the exponent.
+ *     vision: out [B N][ldo] = softmax_t(scale q_n . k_t) v_text, text_mask [B T] or NULL excludes padded text keys.
+ *     text:   out [B T][ldo] = softmax_n(scale q_n . k_t) v_vision over ALL N image keys, vision_mask [B N] or NULL excludes padded
+ *             image keys.  The keys are cut into nchunks = ceil(N / chunk) chunks, chunk = omg_attn_bi_text_chunk(N) (a function of
+ *             N alone: 64 up to N = 4096, then the multiple of 64 that gives at most 64 chunks); every chunk's maximum, sum and
+ *             accumulator [T, 256] go to the workspace in fp32 (omg_attn_bi_text_ws_floats floats, 16-byte aligned) and a second
+ *             launch folds them in ascending chunk order.  A chunk whose keys are all excluded folds in with weight 0.
+ *   The library subtracts the global maximum (vision) or the row maximum (text) and clamps the scores to +- 50000 before its
+ *   softmaxes.  The shifts cancel in a softmax; the CLAMP IS NOT REPRODUCED: results differ from the library's only where the scores
+ *   of one softmax spread by more than 5e4.  A row whose keys are ALL excluded is NaN in the library and UNDEFINED (finite) here; the
+ *   model never makes one.
+ *
+ * omg_attn_masked: O [B Nq][ldo] = softmax(scale Q K^T under mask) V per head, head_dim 64, Nq, Nk <= 256, mask [B Nq Nk] bytes (the
+ *   same for every head) or NULL: the text enhancer's self-attention under the phrase block mask.  Q, K, V, O: rows of ld* elements,
+ *   samples *_bstride elements apart, head h at column 64 h.  A fully excluded row is undefined (finite).
+ *
+ * All three attentions: scores, softmax and P V in fp32 on 16-bit MFMA operands; the probabilities are rounded to the storage type
+ * for the second product and summed AS ROUNDED; the keys run through LDS in tiles of 64 under an online softmax.
+ * ---------------------------------------------------------------------- */
+typedef struct {
+  int32_t dtype;
+  int32_t B, N, Nq;           /* value rows and query rows per sample                */
+  int32_t heads, head_dim;    /* head_dim == 32                                       */
+  int32_t L, points;          /* 1 <= L <= 4, points == 4                             */
+  int32_t H[4], W[4], start[4];
+  const void* value; int64_t ldv;
+  const uint8_t* mask;        /* [B, N] or NULL                                       */
+  const void* ow; int64_t ldow;
+  const float* ref;           /* [B, Nq, L, 2]                                        */
+  void* out; int64_t ldo;
+} omg_msdeform_args;
+
+int omg_msdeform_attn(const omg_msdeform_args* a, void* stream);
+int omg_attn_bi_vision(int dtype, int B, int heads, int N, int T, const void* vis, int64_t ld_vis, int64_t vis_bstride,
+                       const void* txt, int64_t ld_txt, int64_t txt_bstride, const uint8_t* text_mask, float scale,
+                       void* out, int64_t ldo, int64_t o_bstride, void* stream);
+int omg_attn_bi_text_chunk(int N);
+int64_t omg_attn_bi_text_ws_floats(int B, int heads, int T, int N);
+int omg_attn_bi_text(int dtype, int B, int heads, int N, int T, const void* vis, int64_t ld_vis, int64_t vis_bstride,
+                     const void* txt, int64_t ld_txt, int64_t txt_bstride, const uint8_t* vision_mask, float scale,
+                     float* workspace, void* out, int64_t ldo, int64_t o_bstride, void* stream);
+int omg_attn_masked(int dtype, int B, int heads, int Nq, int Nk, const void* Q, int64_t ldq, int64_t q_bstride,
+                    const void* K, int64_t ldk, int64_t k_bstride, const void* V, int64_t ldv, int64_t v_bstride,
+                    const uint8_t* mask, float scale, void* O, int64_t ldo, int64_t o_bstride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,8 @@ _SAM_VIT = ("SamImageEncoderViT",)
 _SEGMENT_ANYTHING = ("Sam", "SamPredictor", "ResizeLongestSide", "build_sam", "build_sam_vit_h", "build_sam_vit_l", "build_sam_vit_b", "sam_model_registry")
 _DPT = ("DPTForDepthEstimation", "DPTImageProcessor", "DPTFeatureExtractor", "depth_condition")
 _SWIN = ("SwinBackbone", "swin_from_groundingdino")
-__all__ = list(_SAM) + list(_SAM_VIT) + list(_SEGMENT_ANYTHING) + list(_DPT) + list(_SWIN)
+_GDINO = ("GroundingDinoEncoder", "GroundingDinoEncoderOutput")
+__all__ = list(_SAM) + list(_SAM_VIT) + list(_SEGMENT_ANYTHING) + list(_DPT) + list(_SWIN) + list(_GDINO)
 
 
 def __getattr__(name):          # the segmenter's public names, imported on first use (omg_amd.sam pulls in torch and the kernels' bindings)
@@ -27,4 +28,7 @@ def __getattr__(name):          # the segmenter's public names, imported on firs
     if name in _SWIN:
         from . import swin
         return getattr(swin, name)
+    if name in _GDINO:
+        from . import gdino
+        return getattr(gdino, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

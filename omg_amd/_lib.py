@@ -116,6 +116,17 @@ class VMapArgs(C.Structure):
     ]
 
 
+class MsdeformArgs(C.Structure):
+    _fields_ = [
+        ("dtype", c_i32), ("B", c_i32), ("N", c_i32), ("Nq", c_i32),
+        ("heads", c_i32), ("head_dim", c_i32), ("L", c_i32), ("points", c_i32),
+        ("H", c_i32 * 4), ("W", c_i32 * 4), ("start", c_i32 * 4),
+        ("value", c_vp), ("ldv", c_i64), ("mask", c_vp),
+        ("ow", c_vp), ("ldow", c_i64), ("ref", c_vp),
+        ("out", c_vp), ("ldo", c_i64),
+    ]
+
+
 class StepArgs(C.Structure):
     _fields_ = [
         ("C", c_i32), ("H", c_i32), ("W", c_i32), ("Hm", c_i32), ("Wm", c_i32),
@@ -190,6 +201,14 @@ SYMBOLS = {
     "omg_attn_swin": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_f32, c_vp, c_i64, c_vp]),
     "omg_swin_patch_embed": (c_i32, [c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp]),
     "omg_swin_merge_ln": (c_i32, [c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp]),
+    "omg_msdeform_attn": (c_i32, [C.POINTER(MsdeformArgs), c_vp]),
+    "omg_attn_bi_vision": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_f32, c_vp, c_i64, c_i64, c_vp]),
+    "omg_attn_bi_text_chunk": (c_i32, [c_i32]),
+    "omg_attn_bi_text_ws_floats": (c_i64, [c_i32, c_i32, c_i32, c_i32]),
+    "omg_attn_bi_text": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_f32, c_vp, c_vp, c_i64, c_i64,
+                                 c_vp]),
+    "omg_attn_masked": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_f32,
+                                c_vp, c_i64, c_i64, c_vp]),
     "omg_debug_set_glds": (None, [c_i32]),
     "omg_debug_set_gemm_variant": (None, [c_i32]),
     "omg_debug_choose_variant": (c_i32, [c_i32, c_i32, c_i32, c_i32]),

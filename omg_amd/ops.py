@@ -973,6 +973,127 @@ def swin_merge_ln(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps:
     return y
 
 
+def _bytes(m: Optional[torch.Tensor], shape, device) -> Optional[torch.Tensor]:
+    """A [..] bool / uint8 mask (1 = valid / attend) as contiguous bytes on ``device``; None stays None."""
+    if m is None:
+        return None
+    assert tuple(m.shape) == tuple(shape) and m.dtype in (torch.bool, torch.uint8) and m.device == device, (tuple(m.shape), m.dtype)
+    m = m.contiguous()
+    return m.view(torch.uint8) if m.dtype == torch.bool else m
+
+
+def msdeform_attn(value: torch.Tensor, ow: torch.Tensor, ref: torch.Tensor, spatial_shapes: Sequence[Tuple[int, int]], *, heads: int = 8,
+                  points: int = 4, mask: Optional[torch.Tensor] = None, level_start: Optional[Sequence[int]] = None,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Multi-scale deformable attention between its Linear layers.  ``value`` [B, N, heads*32] (the rows of value_proj; a row stride that
+    is a multiple of 8 is fine), ``ow`` [B, Nq, heads*L*12] = sampling_offsets | attention_weights of the queries, ``ref`` [B, Nq, L, 2]
+    fp32 (x, y), ``spatial_shapes`` [(H_l, W_l)] with level l at rows ``level_start[l]`` (default: one after the other), ``mask`` [B, N]
+    bool / uint8, 0 = the value row reads as zeros -> [B, Nq, heads*32].  omg_msdeform_attn."""
+    _dev(value)
+    B, N, Wd = value.shape
+    Nq = ow.shape[1]
+    Lv = len(spatial_shapes)
+    if not 1 <= Lv <= 4:
+        raise L.OmgHipError(f"msdeform_attn: {Lv} levels; the kernel takes 1 to 4")
+    assert Wd % heads == 0 and value.stride(2) == 1 and (B == 1 or value.stride(0) == N * value.stride(1))
+    assert ow.shape == (B, Nq, heads * Lv * points * 3) and ow.stride(2) == 1 and (B == 1 or ow.stride(0) == Nq * ow.stride(1)) and ow.dtype == value.dtype
+    assert ref.shape == (B, Nq, Lv, 2) and ref.dtype == torch.float32 and ref.is_contiguous() and ref.is_cuda
+    mask = _bytes(mask, (B, N), value.device)
+    if level_start is None:
+        level_start, s = [], 0
+        for (h_, w_) in spatial_shapes:
+            level_start.append(s)
+            s += int(h_) * int(w_)
+    if out is None:
+        out = torch.empty((B, Nq, Wd), dtype=value.dtype, device=value.device)
+    assert out.shape[:2] == (B, Nq) and out.shape[2] >= Wd and out.stride(2) == 1 and out.dtype == value.dtype
+    assert B == 1 or out.stride(0) == Nq * out.stride(1)
+    a = L.MsdeformArgs()
+    a.dtype, a.B, a.N, a.Nq, a.heads, a.head_dim, a.L, a.points = _dt(value), B, N, Nq, heads, Wd // heads, Lv, points
+    for i, (h_, w_) in enumerate(spatial_shapes):
+        a.H[i], a.W[i], a.start[i] = int(h_), int(w_), int(level_start[i])
+    a.value, a.ldv, a.mask = value.data_ptr(), value.stride(1), _p(mask)
+    a.ow, a.ldow, a.ref = ow.data_ptr(), ow.stride(1), ref.data_ptr()
+    a.out, a.ldo = out.data_ptr(), out.stride(1)
+    t0 = _PROF.begin() if _PROF is not None else None
+    L.check(L.lib().omg_msdeform_attn(C.byref(a), _stream()), "omg_msdeform_attn")
+    if _PROF is not None:
+        _PROF.end("msdeform_attn", 2.0 * B * Nq * Wd * Lv * points * 4, t0, ("msdeform_attn", Nq, N, Lv))
+    return out
+
+
+def _bi_operands(vis: torch.Tensor, txt: torch.Tensor, heads: int):
+    _dev(vis)
+    B, N, Wv = vis.shape
+    T = txt.shape[1]
+    assert Wv == 2 * heads * 256 and txt.shape == (B, T, Wv) and txt.dtype == vis.dtype and vis.stride(2) == 1 and txt.stride(2) == 1
+    return B, N, T
+
+
+def attn_bi_vision(vis: torch.Tensor, txt: torch.Tensor, heads: int, scale: float, *, text_mask: Optional[torch.Tensor] = None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The image side of GroundingDINO's bi-attention at head_dim 256: ``vis`` [B, N, 2*heads*256] = vision q | vision v, ``txt``
+    [B, T <= 256, 2*heads*256] = text k | text v -> softmax over the text keys (``text_mask`` [B, T], 0 = padded) times the text values,
+    [B, N, heads*256].  omg_attn_bi_vision."""
+    B, N, T = _bi_operands(vis, txt, heads)
+    text_mask = _bytes(text_mask, (B, T), vis.device)
+    if out is None:
+        out = torch.empty((B, N, heads * 256), dtype=vis.dtype, device=vis.device)
+    assert out.shape == (B, N, heads * 256) and out.stride(2) == 1 and out.dtype == vis.dtype
+    t0 = _PROF.begin() if _PROF is not None else None
+    L.check(L.lib().omg_attn_bi_vision(_dt(vis), B, heads, N, T, vis.data_ptr(), vis.stride(1), vis.stride(0), txt.data_ptr(), txt.stride(1),
+                                       txt.stride(0), _p(text_mask), scale, out.data_ptr(), out.stride(1), out.stride(0), _stream()),
+            "omg_attn_bi_vision")
+    if _PROF is not None:
+        _PROF.end("attn_bi_vision", 4.0 * B * heads * N * T * 256, t0, ("attn_bi_vision", N, T))
+    return out
+
+
+def attn_bi_text_chunk(N: int) -> int:
+    """Image keys per workgroup of :func:`attn_bi_text`: a function of N alone.  omg_attn_bi_text_chunk."""
+    return int(L.lib().omg_attn_bi_text_chunk(int(N)))
+
+
+def attn_bi_text(vis: torch.Tensor, txt: torch.Tensor, heads: int, scale: float, *, vision_mask: Optional[torch.Tensor] = None,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The text side of the bi-attention: softmax over all N image keys (``vision_mask`` [B, N], 0 = padded) times the vision values,
+    [B, T, heads*256].  Operands as :func:`attn_bi_vision`; the chunk partials live in a workspace allocated per call (as
+    :func:`groupnorm`'s).  omg_attn_bi_text."""
+    B, N, T = _bi_operands(vis, txt, heads)
+    vision_mask = _bytes(vision_mask, (B, N), vis.device)
+    if out is None:
+        out = torch.empty((B, T, heads * 256), dtype=vis.dtype, device=vis.device)
+    assert out.shape == (B, T, heads * 256) and out.stride(2) == 1 and out.dtype == vis.dtype
+    ws = torch.empty(max(int(L.lib().omg_attn_bi_text_ws_floats(B, heads, T, N)), 4), dtype=torch.float32, device=vis.device)
+    t0 = _PROF.begin() if _PROF is not None else None
+    L.check(L.lib().omg_attn_bi_text(_dt(vis), B, heads, N, T, vis.data_ptr(), vis.stride(1), vis.stride(0), txt.data_ptr(), txt.stride(1),
+                                     txt.stride(0), _p(vision_mask), scale, ws.data_ptr(), out.data_ptr(), out.stride(1), out.stride(0),
+                                     _stream()), "omg_attn_bi_text")
+    if _PROF is not None:
+        _PROF.end("attn_bi_text", 4.0 * B * heads * N * T * 256, t0, ("attn_bi_text", N, T))
+    return out
+
+
+def attn_masked(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: float, *, mask: Optional[torch.Tensor] = None,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``softmax(q k^T scale under mask) v`` per head at head_dim 64: ``q`` [B, Nq, heads*64], ``k`` / ``v`` [B, Nk, heads*64], Nq, Nk <= 256,
+    ``mask`` [B, Nq, Nk] bool / uint8 (1 = attend, the same for every head) -> [B, Nq, heads*64].  Column slices of a projection buffer
+    are fine.  omg_attn_masked."""
+    _dev(q)
+    B, Nq, Wd = q.shape
+    Nk = k.shape[1]
+    assert Wd == heads * 64 and k.shape == (B, Nk, Wd) and v.shape == (B, Nk, Wd) and k.dtype == q.dtype and v.dtype == q.dtype
+    assert q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1
+    mask = _bytes(mask, (B, Nq, Nk), q.device)
+    if out is None:
+        out = torch.empty((B, Nq, Wd), dtype=q.dtype, device=q.device)
+    assert out.shape == (B, Nq, Wd) and out.stride(2) == 1 and out.dtype == q.dtype
+    L.check(L.lib().omg_attn_masked(_dt(q), B, heads, Nq, Nk, q.data_ptr(), q.stride(1), q.stride(0), k.data_ptr(), k.stride(1), k.stride(0),
+                                    v.data_ptr(), v.stride(1), v.stride(0), _p(mask), scale, out.data_ptr(), out.stride(1), out.stride(0),
+                                    _stream()), "omg_attn_masked")
+    return out
+
+
 def conv3x3_nhwc_ex(x: torch.Tensor, w: torch.Tensor, *, stride: int = 1, bias: Optional[torch.Tensor] = None, act: int = 0,
                     residual: Optional[torch.Tensor] = None, relu_in: bool = False, same: bool = False,
                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
