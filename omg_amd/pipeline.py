@@ -22,13 +22,15 @@ MI355X-first differences from the reference's loop, all value-preserving:
 """
 from __future__ import annotations
 
+import warnings
+from collections import namedtuple
 from types import SimpleNamespace
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import torch
 
 from . import _lib as L
-from . import ops
+from . import ops, parallel
 from .attention import Attention, RegionControlNet_AttnProcessor
 from .lora import LoraBank
 from .modules import LoraState, pointer_epoch
@@ -196,6 +198,58 @@ class StageCache:
     def get_history(self, key: str) -> Optional[torch.Tensor]:
         return self.history.get(key) if key in self.entries else None
 
+    # ---- one call's use of the cache: its keys (stage_cache_keys below), what it resumes from, what it stores after a step
+    # per request: latents (+ multistep history); drop_unc0: per step k the (n, C, H, W) latents / model inputs of the base samples
+    Resume = namedtuple("Resume", "first latents history base_traj", defaults=(0, None, None, None))
+
+    def lookup(self, keys: Sequence[str], plan: "CallPlan", device, dtype) -> "StageCache.Resume":
+        """A stage-2 call resumes at the first fused step when EVERY request's key is there (with a multistep scheduler: and its history);
+        ``plan.drop_unc0``: with the base samples' trajectory when every request has all of it."""
+        hit = [self.get(k) for k in keys]
+        hist = None
+        if plan.multistep:      # the first resumed step also reads the data prediction of the step in front of it
+            hist = [self.get_history(k) for k in keys]
+            hit = [h if m is not None else None for h, m in zip(hit, hist)]
+        if not (plan.fuse_possible and all(h is not None for h in hit)):
+            self.misses += len(keys)
+            return self.Resume()
+        first, base_traj = plan.fusion_start + 1, None                   # every request resumes: the plain steps are not run at all
+        self.hits += len(keys)
+        if plan.drop_unc0:
+            bases = [self.get_base(k, first, plan.S) for k in keys]
+            if all(b is not None for b in bases):
+                base_traj = {k: (torch.cat([b[k][0] for b in bases]).to(device), torch.cat([b[k][1] for b in bases]).to(device=device, dtype=dtype))
+                             for k in range(first + 1, plan.S + 1)}
+        return self.Resume(first, hit, hist, base_traj)
+
+    def store(self, keys: Sequence[str], i: int, fusion_start: int, lat: torch.Tensor, xin: torch.Tensor, x0_hist: Optional[torch.Tensor]) -> None:
+        """After step i of a call that started at step 0: ``lat`` (2n, ...) latents, ``xin`` next model inputs, ``x0_hist`` of a multistep scheduler."""
+        if i == fusion_start:                                           # the latents entering the first fused step of a stage-2 call
+            for j, k in enumerate(keys):
+                self.put(k, lat[2 * j: 2 * j + 2])
+                if x0_hist is not None:                                 # ... and the data prediction that step reads besides them
+                    self.put_history(k, x0_hist[2 * j: 2 * j + 2])
+        if i >= fusion_start:                                           # ... and the base sample's way from there on (drop_unc0)
+            for j, k in enumerate(keys):
+                self.put_base(k, i + 1, lat[2 * j: 2 * j + 1], xin[4 * j + 2: 4 * j + 3])
+
+
+def stage_cache_keys(p: "CallPlan", sizes: tuple, unet, bank, controller, controlnet, t) -> List[str]:
+    """Per request, the digest of everything that determines the latents entering step ``fusion_start + 1`` (see :class:`StageCache`);
+    ``p``: the call's plan; ``sizes``: height, width, original size, the negative micro-conditioning or None, crop, target size, dtype."""
+    common = (p.S, p.guidance_scale, p.scheduler_name, p.fusion_start) + sizes + (
+              tuple(p.main_adapters), p.main_scale, p.lora_mode if p.main_adapters else None,
+              id(unet), getattr(unet, "weights_version", 0), getattr(bank, "version", None) if p.main_adapters else None,
+              None if controller is None else (type(controller).__name__, p.pure_controller, getattr(controller, "num_self_replace", None)),
+              None if not p.use_cn else (id(controlnet), getattr(controlnet, "weights_version", 0), p.cn_scale,
+                                         tuple(k[0] for k in p.cn_keep[: p.fusion_start + 1])))
+    keys = []
+    for j in range(p.n):
+        cn_img = None if not p.use_cn else (t.cn_image if t.cn_image.shape[0] == 1 else t.cn_image[j: j + 1])
+        z_key = (t.zid_l[j],) if p.stochastic else ()        # a trajectory is valid for the same noise only
+        keys.append(StageCache.digest(common, t.coef, t.lats[j], t.ehs_l[j], t.text_l[j], cn_img, *z_key))
+    return keys
+
 
 # Parameters of the reference's ``__call__`` (lora_pipeline.py:212-255, instantid_pipeline.py:215-259) that change ITS output when they leave their
 # default and that this engine does not implement: name -> (the default, where the reference uses it).  A non-default value is REFUSED — ignoring
@@ -230,6 +284,554 @@ class StableDiffusionXLPipelineOutput(SimpleNamespace):
     pass
 
 
+class CallPlan(SimpleNamespace):
+    """Every decision ``generate_many`` makes before it touches a device buffer, made by the constructor from plain values: which rows a
+    step runs, which LoRA slot each row gets, which mode falls back to the full batch, what is refused, what keys the engine.  Two
+    fields are settled on the device afterwards: ``twin`` survives only if the two samples' embeddings compare equal, and
+    :meth:`with_drop0` follows the stage cache's answer."""
+
+    def __init__(self, *, n: int, lora_list: Sequence[str], S: int, stage, fusion_start: int = FUSION_START, active: Sequence[int] = (),
+                 scheduler_cls=DDIMScheduler, stochastic: bool = False, guidance_scale: float = 5.0, use_graph: bool = False,
+                 n_nets: Optional[int] = None, cn_image_shapes=(), controlnet_conditioning_scale=1.0, guess_mode: bool = False,
+                 control_guidance_start=0.0, control_guidance_end=1.0, has_identitynet: bool = False, identitynet_conditioning_scale: float = 1.0,
+                 dedup: bool = False, stage_cache: bool = False, drop_unc0: bool = False, concept_shard=None, has_controller: bool = False,
+                 pure_controller: bool = False, callback: bool = False, callback_steps=None, callback_on_step_end: bool = False,
+                 callback_on_step_end_tensor_inputs=("latents",), has_concept_models: bool = True, shared: bool = True, bank_adapters=None,
+                 bank_mode: Optional[str] = None, lora_mode: str = "merged", concept_lora: bool = True, styleL=None, main_adapters=None,
+                 concept_adapters=None, concept_adapter_scale: float = 1.0, main_scale: float = 1.0):
+        """``n_nets`` / ``cn_image_shapes``: how many ControlNets were passed (None: none) and the shape of each conditioning image (None: missing);
+        ``bank_adapters`` / ``bank_mode``: of ``concept_models.bank`` (None: no bank); ``shared``: the concept UNet is the pipeline's own;
+        the ``has_*`` / callback flags: whether the object was passed.  Everything else as ``generate_many`` takes it."""
+        self.n, self.S, self.fusion_start, self.lora_list, self.active = n, S, fusion_start, tuple(lora_list), tuple(active)
+        self.K, self.Ka = K, Ka = len(self.lora_list), len(self.active)
+        self.cn_image_shapes, self.lora_mode, self.shared = tuple(cn_image_shapes), lora_mode, shared
+        self.guidance_scale, self.idn_scale, self.styleL = float(guidance_scale), float(identitynet_conditioning_scale), bool(styleL)
+        self.scheduler_name, self.stochastic = scheduler_cls.__name__, stochastic      # stochastic: omg_fuse_cfg_step_noise + the per-step noise eng.z
+        self.multistep = issubclass(scheduler_cls, DPMSolverMultistepScheduler)         # omg_fuse_cfg_step_ms + the history buffer eng.x0_hist
+        self.pure_controller, self.drop0 = pure_controller, False
+        # ---- ControlNet plan: one net without guess_mode runs on the engine's original single-net path (twin / shard / stage-cache aware); a list of
+        # nets or guess_mode on the general path `cn_multi` (full batch only)
+        n_cn = n_nets or 0
+        scs = list(controlnet_conditioning_scale) if isinstance(controlnet_conditioning_scale, (list, tuple)) else [controlnet_conditioning_scale] * n_cn
+        if n_nets is not None and (not n_nets or len(cn_image_shapes) != n_nets or len(scs) < n_nets or any(s is None for s in cn_image_shapes)):
+            raise ValueError(f"{n_nets} ControlNet(s) need as many conditioning images and scales (got {len(cn_image_shapes)} image(s), {len(scs)} scale(s))")
+        self.use_cn, self.cn_guess = n_cn == 1 and not guess_mode, bool(guess_mode)
+        self.cn_multi = n_cn > 0 and not self.use_cn
+        self.cn_scale = 1.0 if self.cn_multi else float(scs[0] if self.use_cn else controlnet_conditioning_scale)
+        self.cn_scales = tuple(float(x) for x in scs[:n_cn]) if self.cn_multi else ()
+        # controlnet_keep (lora_pipeline.py:421-428): per step, per net, 0.0 or 1.0
+        self.cn_keep = controlnet_keep(S, control_guidance_start, control_guidance_end, max(1, n_cn))
+        if len(self.cn_keep[0]) != max(1, n_cn):
+            raise ValueError(f"control_guidance_start / _end must be scalars or hold one entry per ControlNet ({max(1, n_cn)})")
+        self.shard = shard = concept_shard if (concept_shard is not None and concept_shard.world > 1) else None
+        if shard is not None and stochastic:
+            raise L.OmgHipError("concept_shard with a stochastic step (Euler-ancestral, DDIM eta > 0) is not built: the ranks would have to agree "
+                                "on the noise; run the unsharded call")
+        self.has_cb = bool(callback or callback_on_step_end)
+        if self.has_cb:
+            if shard is not None:
+                raise L.OmgHipError("callbacks with concept_shard are not built: every rank would have to run the same callback")
+            bad = [k for k in callback_on_step_end_tensor_inputs if k not in _CALLBACK_TENSORS]
+            if bad:
+                raise ValueError(f"callback_on_step_end_tensor_inputs {bad}: only {list(_CALLBACK_TENSORS)} exist (lora_pipeline.py:165)")
+            if callback and (callback_steps is None or int(callback_steps) <= 0):
+                raise ValueError("callback needs a positive callback_steps")
+            dedup, stage_cache, drop_unc0 = False, False, False
+        if self.cn_multi:
+            if shard is not None:
+                raise L.OmgHipError("concept_shard with a list of ControlNets / guess_mode is not built: run the unsharded call")
+            dedup, stage_cache, drop_unc0 = False, False, False        # the general ControlNet path runs the full batch
+        ctl_exact = not has_controller or bool(pure_controller)
+        # a stochastic step gives the two samples of a request different noise from step 0: they are never the same computation
+        self.twin = bool(dedup) and shard is None and not stochastic and ctl_exact
+        self.cn_image_rows = cn_image_shapes[0][0] if self.use_cn else None
+        if self.use_cn and self.cn_image_rows not in (1, n):
+            # one conditioning image per MAIN ROW (4n): the two samples of a request may differ, and the 2n-row twin batch would not divide it
+            # (ADVICE r3); the cache key and drop_unc0's compact rows address images per REQUEST — not built for that layout (the full batch
+            # handles it); neither is used instead of being keyed / indexed wrongly (ADVICE r4)
+            self.twin, stage_cache, drop_unc0 = False, False, False
+        self.fuse_possible = fuse_possible = stage == 2 and Ka > 0 and S > fusion_start + 1
+        self.nm, self.ncn = 4 * n, 2 * Ka * n                       # rows of the main block / the concept block
+        self.nb = self.nm + (self.ncn if fuse_possible else 0)
+        if fuse_possible and not has_concept_models:
+            raise ValueError("stage 2 needs concept_models")
+        # ---- LoRA slots.  Concept passes: set_adapters(lora) or set_adapters([lora, "style"], [0.7, 0.5]) (lora_pipeline.py:588-591).
+        # MAIN pass: inference_lora.py:162-164 loads the style LoRA into the main pipe as well, and the main UNet is called with
+        # cross_attention_kwargs={"scale": 0.8} (:546-566), so with styleL every main sample runs with adapter "style" at PEFT
+        # weight 1.0 x scale — one more slot of the same bank, selected for the main rows in plain AND fused steps.
+        # LoRA scale: the concept UNet is always called with cross_attention_kwargs={'scale': 0.8} (hard-coded, :592-598); the main UNet
+        # (style slot) with the caller's cross_attention_kwargs (:546-566; PEFT's default scale is 1.0)
+        self.main_scale, self.concept_adapter_scale = float(main_scale), float(concept_adapter_scale)
+        # InstantID's concepts are identities (IP-Adapter tokens + IdentityNet), not LoRA adapters: its `lora_list` only counts them
+        self.main_adapters = main_adapters = [(str(a), float(w)) for a, w in (main_adapters or ())] or ([("style", 1.0)] if styleL else [])
+        self.concept_adapters = concept_adapters = [(str(a), float(w)) for a, w in (concept_adapters or ())]
+        if concept_lora and concept_adapters:
+            raise ValueError("concept_adapters is the InstantID flow's 'whatever is active' rule; the LoRA flow selects adapters per concept (lora_list)")
+        self.use_bank = use_bank = bank_adapters is not None and bool(concept_lora or concept_adapters or main_adapters)
+        combos = []
+        if fuse_possible and concept_lora:
+            combos = [((self.lora_list[c], 0.7), ("style", 0.5)) if styleL else ((self.lora_list[c], 1.0),) for c in self.active]
+        scales = [CONCEPT_LORA_SCALE] * len(combos)
+        if fuse_possible and concept_adapters:              # one combination for every concept row
+            combos, scales = [tuple(concept_adapters)], [self.concept_adapter_scale]
+        self.main_slot = -1
+        if main_adapters:
+            if not use_bank or any(a not in bank_adapters for a, _ in main_adapters):
+                raise ValueError(f"adapters {[a for a, _ in main_adapters]} on the main pass need concept_models with a LoraBank holding them"
+                                 + (" (styleL=True: the adapter named 'style')" if styleL else ""))
+            self.main_slot = len(combos)
+            combos = combos + [tuple(main_adapters)]
+            scales.append(self.main_scale)
+        if concept_adapters and (not use_bank or any(a not in bank_adapters for a, _ in concept_adapters)):
+            raise ValueError(f"concept_adapters {[a for a, _ in concept_adapters]} are not in concept_models' LoraBank")
+        self.combos, self.scales, self.slots = combos, scales, []
+        if fuse_possible:
+            if not use_bank or not (concept_lora or concept_adapters):
+                self.slots = [-1] * self.ncn
+            elif concept_adapters:
+                self.slots = [0] * self.ncn
+            else:
+                self.slots = [s for _ in range(n) for s in range(Ka) for _ in range(2)]
+        self.merged = merged = use_bank and (lora_mode if combos else bank_mode) == "merged"      # the caller builds the bank for `combos` in `lora_mode`
+        self.batched = batched = fuse_possible and (not use_bank or merged) and shared
+        if use_graph and not (not use_bank or merged) and (fuse_possible or self.main_slot >= 0):
+            raise L.OmgHipError("use_graph needs lora_mode='merged' (segment-mode K/V projections are not pointer-stable)")
+        self.use_idn = use_idn = has_identitynet and fuse_possible
+        if use_idn and not batched:
+            raise L.OmgHipError("identitynet runs in the batched mode only: merged / no LoRA, and concept_models built on the pipeline's own "
+                                "UNet (omg_amd.compat's from_pretrained shares it between the main and the concept pipe)")
+        if shard is not None and ((fuse_possible and not batched) or use_idn or not ctl_exact):
+            raise L.OmgHipError("concept_shard needs the batched step (merged / no LoRA on one shared UNet), a pure-replacement controller and no IdentityNet")
+        self.stage_cache = bool(stage_cache) and shard is None and S > fusion_start + 1
+        self.drop_unc0 = bool(drop_unc0) and batched and not use_idn and ctl_exact
+
+    def replace(self, **fields) -> "CallPlan":
+        q = CallPlan.__new__(CallPlan)
+        vars(q).update(vars(self), **fields)
+        return q
+
+    def with_drop0(self) -> "CallPlan":
+        """The resumed call without ``unc0``: the compact-row machinery of the concept shard, on ONE rank — main units of three rows
+        [unc1, cond0, cond1]."""
+        return self.replace(drop0=True, shard=parallel.ConceptShard(rank=0, world=1), twin=False)
+
+    def engine_key(self, shapes_and_ids: tuple = ()) -> tuple:
+        """``shapes_and_ids``: what the plan does not decide on — dtype, the shapes of the call's tensors, id() of the models and the controller"""
+        return (self.n, self.S, self.K, self.active, self.fuse_possible, self.fusion_start, self.scheduler_name, self.guidance_scale, self.batched,
+                self.styleL, tuple(self.main_adapters), tuple(self.concept_adapters), self.concept_adapter_scale, self.main_scale, self.lora_list,
+                self.cn_scale, self.idn_scale, self.twin, (self.shard.rank, self.shard.world) if self.shard is not None else None, self.drop0,
+                self.stochastic, None if not self.cn_multi else (self.cn_image_shapes, self.cn_guess)) + shapes_and_ids
+
+
+
+def all_step_embeddings(net, ts: torch.Tensor, text: torch.Tensor, tids: torch.Tensor) -> torch.Tensor:
+    """emb[i] for every step in one batched pass: (S, rows, 4*C0).  Depends only on (t_i, pooled text, time ids) and on the embedding
+    layers of ``net``, the model that will consume it: the UNet (the concept pipe's, when it is not the main one), a ControlNet, the IdentityNet."""
+    S, rows = ts.numel(), text.shape[0]
+    t_all = ts.reshape(S, 1).expand(S, rows).reshape(-1).contiguous()
+    return net.time_embed(t_all, S * rows, text.repeat(S, 1), tids.repeat(S, 1)).view(S, rows, -1)
+
+
+def _fill(dst: torch.Tensor, srcs: Sequence[torch.Tensor], dim: int, rows: Optional[torch.Tensor] = None) -> None:
+    """dst <- the tensors ``srcs`` laid end to end along ``dim`` (of each its ``rows`` along ``dim`` only), in place, one copy each"""
+    srcs = [s if rows is None else s.index_select(dim, rows) for s in srcs]
+    for d, s in zip(dst.split([s.shape[dim] for s in srcs], dim), srcs):
+        d.copy_(s)
+
+
+class RowSet:
+    """One set of rows a step runs a UNet forward over — the main rows, the batched main + concept rows, the twin rows of ``dedup``, the
+    compact rows of a shard rank or of ``drop_unc0``.  Members: model input ``x`` and output ``y``, text states ``ehs``, the per-step embedding
+    table ``emb`` with its current-step row buffer ``emb_cur``, the LoRA ``state``, the keywords ``kw`` of the forward (``omg_images`` = ``n_images``,
+    ``omg_main_batch`` = ``main_batch``), and for a ControlNet on the set's first ``n_main`` rows its embedding table ``cn_emb`` with ``cn_emb_cur``
+    and its conditioning image ``cn_image``.  Static buffers, allocated once and refilled in place by :meth:`load`: captured graphs point at them."""
+
+    def __init__(self, rows: int, n_images: int, main_batch: int = 4, *, chw, ctx, S, D, dtype, device, x=None, y=None, n_main: int = 0,
+                 cn_image=None, cn_image_shape=None):
+        """``x`` / ``y``: views of a wider buffer this set shares; ``cn_image``: another set's image to share, ``cn_image_shape``: one of its own"""
+        self.rows, self.n_images, self.main_batch, self.n_main = rows, n_images, main_batch, n_main
+        self.x = torch.empty((rows,) + chw, dtype=dtype, device=device) if x is None else x
+        self.y = torch.empty((rows,) + chw, dtype=torch.float32, device=device) if y is None else y
+        self.ehs = torch.empty((rows,) + ctx, dtype=dtype, device=device)
+        self.emb = torch.empty((S, rows, D), dtype=dtype, device=device)
+        self.emb_cur = torch.empty((rows, D), dtype=dtype, device=device)
+        self.cn_emb = self.cn_emb_cur = self.cn_image = None
+        if cn_image is not None or cn_image_shape is not None:
+            self.cn_emb = torch.empty((S, n_main, D), dtype=dtype, device=device)
+            self.cn_emb_cur = torch.empty((n_main, D), dtype=dtype, device=device)
+            self.cn_image = torch.empty(cn_image_shape, dtype=torch.float32, device=device) if cn_image is None else cn_image
+            self.cn_x, self.cn_ehs = self.x[:n_main], self.ehs[:n_main]
+
+    def load(self, ehs, emb, state, kw: dict, rows: Optional[torch.Tensor] = None, cn_emb=None, cn_image=None) -> None:
+        """This call's text states and embedding tables (``ehs`` / ``emb``: lists, laid end to end; with ``rows``: those rows of the source),
+        LoRA state and keywords; ``cn_emb``: the table the ControlNet's is taken from likewise, ``cn_image``: the image, unless it is shared."""
+        _fill(self.ehs, ehs, 0, rows)
+        _fill(self.emb, emb, 1, rows)
+        self.state, self.kw = state, dict(kw, omg_main_batch=self.main_batch, omg_images=self.n_images)
+        if self.cn_emb is not None:
+            _fill(self.cn_emb, [cn_emb], 1, None if rows is None else rows[: self.n_main])
+            if cn_image is not None:
+                self.cn_image.copy_(cn_image)
+
+    def refresh(self, eng: "StepEngine") -> None:
+        """cached cross-attention K/V (and ControlNet conditioning features) must be refreshed eagerly: replayed graphs read the stored tensors"""
+        eng.unet.refresh_cross_kv(self.ehs, self.state)
+        if self.cn_emb is not None:
+            eng.controlnet.refresh_cross_kv(self.cn_ehs)
+            eng.controlnet.cond_features(self.cn_image)
+
+    def control(self, eng: "StepEngine") -> list:
+        """The ControlNet's residuals for the set's main rows (lora_pipeline.py:519-536); scale 0 = outside its guidance window: not run"""
+        if self.cn_emb is None or eng.cur_cn == 0.0:
+            return []
+        ops.gather_step(self.cn_emb, eng.step_idx, self.cn_emb_cur)
+        d_, m_ = eng.controlnet(self.cn_x, None, encoder_hidden_states=self.cn_ehs, controlnet_cond=self.cn_image,
+                                conditioning_scale=eng.cur_cn, emb=self.cn_emb_cur)
+        return [(0, self.n_main, d_, m_)]
+
+    def forward(self, eng: "StepEngine", kw: dict, residuals: list) -> None:
+        """y = UNet(x) at the step the DEVICE counter selects, under the set's LoRA state.  ``residuals``: what the caller collected,
+        :meth:`control` 's among them."""
+        if residuals:
+            kw["omg_residuals"] = residuals
+        ops.gather_step(self.emb, eng.step_idx, self.emb_cur)
+        eng.unet.set_lora_state(self.state)
+        try:
+            eng.unet(self.x, None, encoder_hidden_states=self.ehs, cross_attention_kwargs=kw, emb=self.emb_cur, out=self.y)
+        finally:
+            eng.unet.set_lora_state(None)
+
+
+class StepEngine:
+    """The persistent state of one call shape (:meth:`CallPlan.engine_key`): static buffers, the row sets of its steps and the captured
+    step graphs of every regime.  Built once from the plan, :meth:`load` ed with every call's inputs (device-to-device copies; graphs
+    keep their pointers), then :meth:`run_step` per step."""
+
+    def __init__(self, unet, plan: CallPlan, t, controller, controlnet, identitynet, cn_nets, concept_models):
+        """``t``: the tensors of the first call (``generate_many`` gathers them), for their shapes.  The engine holds no reference to the
+        pipeline that owns it: an engine in a reference cycle would be freed, with its captured graphs, whenever the collector runs — a capture included."""
+        p, dev, dt = plan, unet.device, unet.dtype
+        n, S, nm, ncn, nb, D, ctx = p.n, p.S, p.nm, p.ncn, p.nb, t.emb_main.shape[-1], tuple(t.ehs.shape[1:])
+        self.chw = chw = tuple(t.lats[0].shape[1:])
+        self.unet, self.plan = unet, plan
+        self.controller, self.controlnet, self.identitynet, self.cn_nets = controller, controlnet, identitynet, cn_nets
+        # the key holds id()s: keep the objects alive so that an id cannot be recycled for a different object
+        self.refs = (controller, controlnet, identitynet, concept_models, cn_nets)
+        self.graphs, self.warmed, self.pool = {}, set(), None
+        self.coef = torch.empty_like(t.coef)               # the engine's OWN buffer: the scheduler's cached table is shared and read-only
+        self.epoch = pointer_epoch()
+        self.lat = torch.empty((2 * n,) + chw, dtype=torch.float32, device=dev)
+        self.xin = torch.empty((nb,) + chw, dtype=dt, device=dev)
+        # drop0: the rows of `unc0` are never written — zeros, so that the step kernel's (discarded) update of the base sample stays finite
+        self.nout = (torch.zeros if p.drop0 else torch.empty)((nb,) + chw, dtype=torch.float32, device=dev)
+        self.step_idx = torch.zeros(1, dtype=torch.int32, device=dev)
+        # request j's fusion + CFG + scheduler update + next model input: the one-step linear table (DDIM, Euler) or the multistep one with
+        # the request's rows of the history buffer (DPM-Solver++), or the one-step table plus the request's noise (Euler-ancestral, DDIM eta > 0)
+        self.step_op, extra = ops.fuse_cfg_step, [()] * n
+        if p.multistep:      # the previous step's data prediction of every sample (captured graphs point at it); order-1 steps do not read it
+            self.x0_hist = torch.zeros((2 * n,) + chw, dtype=torch.float32, device=dev)
+            self.step_op, extra = ops.fuse_cfg_step_ms, [(self.x0_hist[2 * j: 2 * j + 2],) for j in range(n)]
+        if p.stochastic:     # every step's noise of every sample (captured graphs point at it), refilled in place per call
+            self.z = torch.empty((S, 2 * n) + chw, dtype=torch.float32, device=dev)
+            self.step_op, extra = ops.fuse_cfg_step_noise, [(self.z[:, 2 * j: 2 * j + 2],) for j in range(n)]
+        # per request: its rows of the noise prediction, the latents and the model input, what its step kernel reads besides them, and (per
+        # concept, None without a mask) its concept pairs' rows of the prediction
+        self.per_request = [(self.nout[4 * j: 4 * j + 4], self.lat[2 * j: 2 * j + 2], self.xin[4 * j: 4 * j + 4], extra[j]) for j in range(n)]
+        self.no_regions = [None] * p.K
+        row = {c: nm + 2 * jj for jj, c in enumerate(p.active)} if p.fuse_possible else {}      # request 0's; request j's: 2 Ka j further on
+        self.regions = [[self.nout[row[c] + 2 * p.Ka * j: row[c] + 2 * p.Ka * j + 2] if c in row else None for c in range(p.K)] for j in range(n)]
+        self.masks = [[torch.empty(t.mshape, dtype=torch.float32, device=dev) if c in p.active else None for c in range(p.K)] for _ in range(n)]
+        shape = dict(chw=chw, ctx=ctx, S=S, D=D, dtype=dt, device=dev)
+        self.main = RowSet(nm, n, x=self.xin[:nm], y=self.nout[:nm], n_main=nm, cn_image_shape=p.cn_image_shapes[0] if p.use_cn else None, **shape)
+        if p.fuse_possible:      # the concept rows as a forward of their own (concept_models.unet_batched: un-batched fused steps)
+            self.conc = RowSet(ncn, n, x=self.xin[nm:], y=self.nout[nm:], **shape)
+        if p.batched:
+            self.all = RowSet(nb, n, x=self.xin, y=self.nout, n_main=nm, **shape)
+        if p.twin:      # compact rows [unc, cond] per request for the steps in which the two samples coincide
+            self.twin = RowSet(2 * n, n, n_main=2 * n, cn_image=self.main.cn_image, **shape)
+        if p.cn_multi:
+            rows_cn = 2 * n if p.cn_guess else nm
+            self.cnm_image = [torch.empty(s, dtype=torch.float32, device=dev) for s in p.cn_image_shapes]
+            self.cnm_emb = [torch.empty((S, rows_cn, D), dtype=dt, device=dev) for _ in cn_nets]
+            self.cnm_emb_cur = [torch.empty((rows_cn, D), dtype=dt, device=dev) for _ in cn_nets]
+            if p.cn_guess:      # the conditional rows [cond0, cond1] of every request, compact
+                self.cnm_x = torch.empty((rows_cn,) + chw, dtype=dt, device=dev)
+                self.cnm_ehs = torch.empty((rows_cn,) + ctx, dtype=dt, device=dev)
+        if p.use_idn:
+            self.ip_all = torch.empty((ncn,) + tuple(t.ip_l[0].shape[1:]), dtype=dt, device=dev)
+            self.kps_all = torch.empty((n,) + tuple(t.kps_l[0].shape[1:]), dtype=torch.float32, device=dev)
+            self.idn_emb = torch.empty((S, ncn, D), dtype=dt, device=dev)
+            self.idn_emb_cur = torch.empty((ncn, D), dtype=dt, device=dev)
+        if p.shard is not None:      # per regime (plain / fused): this rank's units, its compact local batch and every rank's row map
+            self.sh = {fz: self._shard_rows(fz, shape) for fz in ((True,) if p.drop0 else (False, True) if p.fuse_possible else (False,))}
+
+    def _shard_rows(self, fused: bool, shape: dict) -> RowSet:
+        """The compact rows of this rank in a plain / fused step, with what the exchange needs: ``mains`` / ``concs`` (its units), ``src``
+        (the rows of the full model input its ``x`` is gathered from), ``dsts`` / ``counts`` (per rank, where its predictions go in the
+        full batch), ``ybuf`` (the equally sized exchange buffer ``y`` is the head of)."""
+        p, n, Ka, nm, dev = self.plan, self.plan.n, self.plan.Ka, self.plan.nm, self.lat.device
+        rank = p.shard.rank
+        if p.drop0:      # every unit on this one rank; a main unit is rows 1..3 of the request's block (`unc0` is not computed)
+            per_rank = [(list(range(n)), [(j, c) for j in range(n) for c in range(Ka)])]
+            mrows = [4 * j + r for j in range(n) for r in (1, 2, 3)]
+            rows = [(mrows + [4 * j + 3 for j, _ in per_rank[0][1] for _ in range(2)],
+                     mrows + [nm + 2 * Ka * j + 2 * c + r for j, c in per_rank[0][1] for r in range(2)])]
+        else:
+            per_rank = parallel.assign_units(n, Ka, fused, p.shard.world)
+            rows = parallel.unit_rows(per_rank, n, Ka)
+        mains, concs = per_rank[rank]
+        src, counts = rows[rank][0], [len(r[1]) for r in rows]
+        n_main = (3 if p.drop0 else 4) * len(mains)      # drop0: [unc1, cond0, cond1] — cond1 borrows Q, K of cond0 = row 1 of the block
+        ybuf = torch.zeros((max(counts),) + self.chw, dtype=torch.float32, device=dev)
+        image = (len(mains) if p.cn_image_rows != 1 else 1,) + p.cn_image_shapes[0][1:] if p.use_cn and n_main else None
+        sh = RowSet(len(src), len(mains), 3 if p.drop0 else 4, y=ybuf[: len(src)], n_main=n_main, cn_image_shape=image, **shape)
+        sh.mains, sh.concs, sh.counts, sh.ybuf = mains, concs, counts, ybuf
+        sh.src = torch.tensor(src, dtype=torch.long, device=dev)
+        sh.dsts = [torch.tensor(r[1], dtype=torch.long, device=dev) for r in rows]
+        return sh
+
+    def lora_state(self, main_rows: int, concept_slots: Sequence[int] = ()) -> Optional[LoraState]:
+        """``main_rows`` rows on the main pass's slot (base weights, or the style slot / ``main_adapters``), then one row per entry of
+        ``concept_slots`` (-1: base weights).  None: base weights throughout."""
+        p = self.plan
+        if not p.use_bank or (p.main_slot < 0 and not concept_slots):
+            return None
+        if p.merged:
+            return self.concept_models.lora_state([p.main_slot + 1] * main_rows + [s + 1 for s in concept_slots], merged=True)
+        return self.concept_models.lora_state([p.main_slot] * main_rows, merged=False)
+
+    def load(self, plan: CallPlan, t, resume: StageCache.Resume, sched, concept_models, cross_attention_kwargs, use_graph: bool) -> None:
+        """Load a call's inputs into the static buffers; ``t``: its tensors as ``generate_many`` gathered them."""
+        p = self.plan = plan
+        self.concept_models, self.use_graph, self.first, self.base_traj = concept_models, use_graph, resume.first, resume.base_traj
+        n, nm, dev, ctl = p.n, p.nm, self.lat.device, self.controller
+        self.lat.copy_(torch.cat(t.lats, dim=0))
+        # t.coef, per call: the key holds the scheduler's class and step count, not its configuration — a re-configured scheduler must
+        self.coef.copy_(t.coef)                            # not meet a cached table.  In place: captured graphs keep the pointer
+        self.step_idx.zero_()
+        if p.stochastic:
+            for j in range(n):
+                self.z[:, 2 * j: 2 * j + 2].copy_(t.z_l[j])
+        for j in range(n):
+            for c in p.active:
+                self.masks[j][c].copy_(t.masks_l[j][c])
+        if resume.latents is not None:                                   # resume (decided in front of the engine)
+            self.lat.copy_(torch.cat([h.to(dev) for h in resume.latents], dim=0))
+            if p.multistep:
+                self.x0_hist.copy_(torch.cat([h.to(dev) for h in resume.history], dim=0))
+            self.step_idx.fill_(self.first)
+            if ctl is not None:
+                ctl.cur_step = self.first                                # the host-side counters the skipped steps would have ticked
+        cin0 = sched.cin0(dev) if self.first == 0 else torch.tensor([sched.cin[self.first]], dtype=torch.float32, device=dev)
+        for nout_j, lat_j, xin_j, _ in self.per_request:
+            ops.scale_model_input(lat_j, cin0, xin_j)
+        main_kw = dict(cross_attention_kwargs or {})
+        main_kw.pop("scale", None)
+        # main-only forwards (plain steps; the main half of un-batched fused steps): base weights, or the style slot
+        self.main.load([t.ehs], [t.emb_main], self.lora_state(nm), main_kw,
+                       cn_emb=all_step_embeddings(self.controlnet, t.ts, t.text, t.tids_main) if p.use_cn else None,
+                       cn_image=t.cn_image.to(device=dev, dtype=torch.float32) if p.use_cn else None)
+        if p.fuse_possible:
+            self.conc.load([t.c_ehs], [t.emb_conc], None, main_kw)
+        if p.batched:
+            self.all.load([t.ehs, t.c_ehs], [t.emb_main, t.emb_conc], self.lora_state(nm, p.slots), main_kw)
+        if p.cn_multi:
+            cond_rows = torch.tensor([4 * j + r for j in range(n) for r in (2, 3)], dtype=torch.long, device=dev)
+            text_cn, tids_cn = t.text, t.tids_main
+            if p.cn_guess:      # add_text_embeds.chunk(2)[1] / add_time_ids.chunk(2)[1] / prompt_embeds.chunk(2)[1] (lora_pipeline.py:497-503)
+                text_cn, tids_cn = text_cn.index_select(0, cond_rows), tids_cn.index_select(0, cond_rows)
+                self.cnm_ehs.copy_(t.ehs.index_select(0, cond_rows))
+            for k_, net in enumerate(self.cn_nets):
+                self.cnm_image[k_].copy_(t.cn_images[k_].to(device=dev, dtype=torch.float32))
+                self.cnm_emb[k_].copy_(all_step_embeddings(net, t.ts, text_cn, tids_cn))
+                if use_graph:
+                    net.refresh_cross_kv(self.cnm_ehs if p.cn_guess else self.main.ehs)
+                    net.cond_features(self.cnm_image[k_])
+        if p.use_idn:
+            self.ip_all.copy_(torch.cat(t.ip_l, dim=0))
+            self.kps_all.copy_(torch.cat(t.kps_l, dim=0))
+            self.idn_emb.copy_(all_step_embeddings(self.identitynet, t.ts, t.ctext, t.tids_conc))
+        if p.twin:
+            rows2 = torch.tensor([4 * j + r for j in range(n) for r in (0, 2)], dtype=torch.long, device=dev)      # unc0, cond0 of each request
+            self.twin.load([t.ehs], [t.emb_main], self.lora_state(2 * n), dict(main_kw, omg_twin=True), rows=rows2, cn_emb=self.main.cn_emb)
+        if p.shard is not None:
+            for fz, sh in self.sh.items():
+                if not sh.rows:
+                    continue
+                src = self.all if fz else self.main
+                image = None if sh.cn_image is None else self.main.cn_image if p.cn_image_rows == 1 else self.main.cn_image[sh.mains]
+                sh.load([src.ehs], [src.emb], self.lora_state(sh.n_main, [jj for _, jj in sh.concs for _ in range(2)]), main_kw,
+                        rows=sh.dsts[p.shard.rank], cn_emb=self.main.cn_emb, cn_image=image)
+                if use_graph:
+                    sh.refresh(self)
+        elif use_graph:
+            if p.twin:
+                self.twin.refresh(self)
+            self.main.refresh(self)
+            if p.batched:
+                self.all.refresh(self)
+            if p.use_idn:
+                self.identitynet.refresh_cross_kv(self.ip_all)
+                self.identitynet.cond_features(self.kps_all)
+                self.unet.refresh_ip_kv(self.ip_all)      # the UNet's own image-prompt K / V^T of the concept samples
+        # the conditioning scales of the CURRENT step (host floats baked into the zero convolutions' epilogues, hence part of the graph regime):
+        # scale * controlnet_keep[i] (lora_pipeline.py:511-517; instantid_pipeline.py:566-578: the one window scales the IdentityNet and the t2i net)
+        self.cur_cn, self.cur_idn, self.cur_multi = p.cn_scale, p.idn_scale, ()
+        # the general prompt-to-prompt edit reads alpha[cur_step] on the device: cur_step == step_idx + offset from here to the end of the
+        # call (a resumed call set cur_step = first above; replays advance the host counter by one per step, as step_idx advances)
+        self.ctl_step_offset = 0
+        if hasattr(ctl, "bind_step_counter"):
+            self.ctl_step_offset = ctl.cur_step - self.first
+            ctl.bind_step_counter(self.step_idx, self.ctl_step_offset)
+
+    def set_step_scales(self, i: int) -> tuple:
+        p, keep = self.plan, self.plan.cn_keep[i]
+        self.cur_cn, self.cur_idn = p.cn_scale * keep[0], p.idn_scale * keep[0]
+        if p.cn_multi:
+            self.cur_multi = tuple(sc * keep[k_] for k_, sc in enumerate(p.cn_scales))
+        return (self.cur_cn if p.use_cn else None, self.cur_idn if p.use_idn else None, self.cur_multi)
+
+    def multi_residuals(self) -> list:
+        """The general ControlNet block of a step: every net of the list on the main rows (guess_mode: on the conditional rows only), residuals
+        summed in list order like MultiControlNetModel.forward — first the nets' residuals among themselves, then onto the skips — and, in
+        guess_mode, no residual for the unconditional rows (lora_pipeline.py:531-535 concatenates zeros)."""
+        p, n, guess = self.plan, self.plan.n, self.plan.cn_guess
+        sum_d = sum_m = None
+        if guess:
+            self.cnm_x.view((n, 2) + self.chw).copy_(self.main.x.view((n, 4) + self.chw)[:, 2:4])
+        for k_, net in enumerate(self.cn_nets):
+            sc = self.cur_multi[k_]
+            if sc == 0.0:
+                continue
+            ops.gather_step(self.cnm_emb[k_], self.step_idx, self.cnm_emb_cur[k_])
+            d_, m_ = net(self.cnm_x if guess else self.main.x, None, encoder_hidden_states=self.cnm_ehs if guess else self.main.ehs,
+                         controlnet_cond=self.cnm_image[k_], conditioning_scale=sc, emb=self.cnm_emb_cur[k_], guess_mode=guess)
+            if sum_d is None:
+                sum_d, sum_m = d_, m_
+            else:
+                for a_, b_ in zip(sum_d + [sum_m], d_ + [m_]):
+                    ops.add_(a_.permute(0, 2, 3, 1), b_.permute(0, 2, 3, 1))
+        if sum_d is None:
+            return []
+        if not guess:
+            return [(0, p.nm, sum_d, sum_m)]
+        return [(4 * j + 2, 4 * j + 4, [d_[2 * j: 2 * j + 2] for d_ in sum_d], sum_m[2 * j: 2 * j + 2]) for j in range(n)]
+
+    def fill_region_inputs(self) -> None:
+        p = self.plan
+        for j in range(p.n):                              # latent_model_input[3:4] duplicated (:583-585), per request
+            r0 = p.nm + 2 * p.Ka * j
+            self.xin[r0: r0 + 2 * p.Ka].copy_(self.xin[4 * j + 3: 4 * j + 4].expand(2 * p.Ka, -1, -1, -1))
+
+    def twin_body(self) -> None:
+        """A step in which samples 0 and 1 of every request are still identical: one [unc, cond] forward per request, the noise
+        prediction written to both samples, then the ordinary CFG + scheduler step on all four rows."""
+        n, chw, tw = self.plan.n, self.chw, self.twin
+        tw.x.view((n, 2) + chw).copy_(self.main.x.view((n, 2, 2) + chw)[:, :, 0])
+        tw.forward(self, dict(tw.kw), tw.control(self))
+        self.main.y.view((n, 2, 2) + chw).copy_(tw.y.view((n, 2, 1) + chw).expand((n, 2, 2) + chw))
+        self.finish(False)
+
+    def step_body(self, fused: bool, twin_step: bool = False) -> None:
+        """One denoising iteration; every per-step quantity is selected by the DEVICE step counter."""
+        if twin_step:
+            return self.twin_body()
+        p = self.plan
+        rs = self.all if fused and p.batched else self.main
+        kw = dict(rs.kw)
+        residuals = self.main.control(self)               # ControlNet on the main samples, whichever set they are forwarded in
+        if p.cn_multi:
+            residuals.extend(self.multi_residuals())
+        if fused and p.batched:
+            self.fill_region_inputs()
+            if p.use_idn:                                 # IdentityNet on the concept samples (instantid_pipeline.py:638-648)
+                if self.cur_idn != 0.0:
+                    ops.gather_step(self.idn_emb, self.step_idx, self.idn_emb_cur)
+                    d_, m_ = self.identitynet(self.xin[p.nm:], None, encoder_hidden_states=self.ip_all, controlnet_cond=self.kps_all,
+                                              conditioning_scale=self.cur_idn, emb=self.idn_emb_cur)
+                    residuals.append((p.nm, p.nb, d_, m_))
+                kw["omg_ip_tokens"], kw["omg_ip_rows"] = self.ip_all, p.nm
+        rs.forward(self, kw, residuals)
+        if fused and not p.batched:
+            self.fill_region_inputs()
+            cs = self.conc
+            ops.gather_step(cs.emb, self.step_idx, cs.emb_cur)
+            self.concept_models.unet_batched(cs.x, None, cs.ehs, p.slots, emb=cs.emb_cur, out=cs.y)
+        self.finish(fused)
+
+    def finish(self, fused: bool) -> None:
+        """Region fusion + CFG + scheduler update + next model input of every request (one launch each)."""
+        last = self.plan.n - 1
+        for j in range(last + 1):
+            self.scheduler_step(j, fuse=fused, region_preds=self.regions[j] if fused else self.no_regions,
+                                masks=self.masks[j] if fused else self.no_regions, advance=(j == last))
+
+    def scheduler_step(self, j: int, **kw) -> None:
+        nout_j, lat_j, xin_j, extra = self.per_request[j]
+        self.step_op(nout_j, lat_j, self.coef, *extra, self.step_idx, guidance_scale=self.plan.guidance_scale, model_input_next=xin_j, **kw)
+
+    def shard_forward(self, fused: bool, _tw: bool = False) -> None:
+        """This rank's units of the step: main blocks first, then concept pairs, as one compact batch."""
+        sh = self.sh[fused]
+        sh.x.copy_(self.main.x.index_select(0, sh.src))
+        sh.forward(self, dict(sh.kw), sh.control(self))
+
+    def run_step(self, i: int) -> None:
+        p = self.plan
+        fused = p.fuse_possible and i > p.fusion_start
+        scales_i = self.set_step_scales(i)
+        if p.shard is None:
+            # twin: the samples part ways at the first fused step (stage 1: never)
+            return self.run_forward(self.step_body, fused, p.twin and not fused, (fused, scales_i))
+        sh = self.sh[fused]
+        if sh.rows:
+            self.run_forward(self.shard_forward, fused, False, ("shard", fused, scales_i))
+        elif self.controller is not None:
+            self.controller.cur_step += 1          # no unit of this step is ours: only the host-side step counter moves
+        p.shard.exchange(sh.ybuf, sh.counts, sh.dsts, self.nout)
+        self.finish(fused)
+        if p.drop0:      # the base samples were not computed: their latents and next model inputs are the stage-1 call's
+            bl, bx = self.base_traj[i + 1]
+            self.lat.view((p.n, 2) + self.chw)[:, 0].copy_(bl)
+            if i + 1 < p.S:
+                self.main.x.view((p.n, 4) + self.chw)[:, 2].copy_(bx)
+
+    def run_forward(self, body: Callable, fused: bool, tw: bool, tag: tuple) -> None:
+        """``body`` eagerly, or — ``use_graph`` — as the captured graph of its regime: eager on first sight, captured on the second, replayed after"""
+        if not self.use_graph:
+            body(fused, tw)
+            return
+        controller = self.controller
+        if self.epoch != pointer_epoch():         # a weight image or cached K/V the graphs point at was freed or re-allocated
+            self.graphs.clear()
+            self.warmed.clear()
+            self.pool = None                      # the pool dies with its last graph: a later capture must open a new one
+            self.epoch = pointer_epoch()
+        win = controller._self_window() if controller is not None and hasattr(controller, "_self_window") else None
+        # the cross edit's kind at this step ("borrow" / "own" / "mixed": different launches); WITHIN a kind one graph serves every
+        # step, because the edit's alpha row is selected on the device through the step counter bound in load() (+ its host offset)
+        ck = (controller.cross_kind(), self.ctl_step_offset) if hasattr(controller, "cross_kind") else None
+        regime = tag + (win, tw, ck)
+        g = self.graphs.get(regime)
+        if g is not None:
+            g.replay()
+            if controller is not None:
+                controller.cur_step += 1          # the replayed graph does not run the host-side counters
+            return
+        if regime not in self.warmed:             # first step of a regime runs eagerly (lazy inits, caches)
+            body(fused, tw)
+            self.warmed.add(regime)
+            return
+        g = torch.cuda.CUDAGraph()
+        torch.cuda.synchronize()
+        with torch.cuda.graph(g, pool=self.pool):
+            body(fused, tw)                       # records the step; host counters tick as in eager mode
+        if self.pool is None:
+            self.pool = g.pool()
+        self.graphs[regime] = g
+        g.replay()
+
+
 class LoraMultiConceptPipeline:
     """See the module docstring.  ``__call__`` keeps the reference's single-request signature; ``generate_many`` runs
     several independent requests in lock-step through ONE batched UNet forward per step (images are independent,
@@ -241,7 +843,7 @@ class LoraMultiConceptPipeline:
         self.encode_prompt = encode_prompt
         self.vae_decode = vae_decode
         self.vae_scale_factor = 8
-        self._engines: Dict[Tuple, SimpleNamespace] = {}      # call shape -> static buffers + captured step graphs, LRU
+        self._engines: Dict[Tuple, StepEngine] = {}           # call shape -> static buffers + captured step graphs, LRU
         self.max_engines = 8                                   # a few hundred MB of buffers each (+ graph pools): raise for servers with many shapes
         self.engine_evictions = 0
 
@@ -267,14 +869,6 @@ class LoraMultiConceptPipeline:
     def _add_time_ids(original_size, crops, target_size, n, device):
         ids = list(original_size) + list(crops) + list(target_size)
         return torch.tensor([ids] * n, dtype=torch.float32, device=device)
-
-    def _all_step_embeddings(self, ts: torch.Tensor, text: torch.Tensor, tids: torch.Tensor, unet=None) -> torch.Tensor:
-        """emb[i] for every step in one batched pass: (S, B, 4*C0).  Depends only on (t_i, pooled text, time ids) and on the
-        embedding layers of the UNet that will consume it (``unet``: the concept pipe's, when it is not the main one)."""
-        S, B = ts.numel(), text.shape[0]
-        t_all = ts.reshape(S, 1).expand(S, B).reshape(-1).contiguous()
-        emb = (unet or self.unet).time_embed(t_all, S * B, text.repeat(S, 1), tids.repeat(S, 1))
-        return emb.view(S, B, -1)
 
     # ------------------------------------------------------------------ the reference's call signature
     @torch.no_grad()
@@ -470,52 +1064,117 @@ class LoraMultiConceptPipeline:
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor
         lora_list = list(lora_list or [])
-        K = len(lora_list)
         S = num_inference_steps
         self.scheduler.set_timesteps(S, device=dev)
-        ts = self.scheduler.timesteps.to(torch.float32)
         original_size = original_size or (height, width)
         target_size = target_size or (height, width)
-        Cl = self.unet.config.in_channels
-        # ---- ControlNet plan: one net without guess_mode runs on the engine's original single-net path (twin / shard / stage-cache aware); a list of
-        # nets or guess_mode on the general path `cn_multi` below (full batch only)
-        cn_multi = None
-        n_cn = 0
-        if controlnet is not None:
-            nets = list(controlnet.nets) if hasattr(controlnet, "nets") else list(controlnet) if isinstance(controlnet, (list, tuple)) else [controlnet]
-            imgs = list(controlnet_image) if isinstance(controlnet_image, (list, tuple)) else [controlnet_image]
-            scs = list(controlnet_conditioning_scale) if isinstance(controlnet_conditioning_scale, (list, tuple)) else [controlnet_conditioning_scale] * len(nets)
-            if not nets or len(imgs) != len(nets) or len(scs) < len(nets) or any(im is None for im in imgs):
-                raise ValueError(f"{len(nets)} ControlNet(s) need as many conditioning images and scales (got {len(imgs)} image(s), {len(scs)} scale(s))")
-            n_cn = len(nets)
-            if n_cn == 1 and not guess_mode:
-                controlnet, controlnet_image, controlnet_conditioning_scale = nets[0], imgs[0], float(scs[0])
-            else:
-                cn_multi = SimpleNamespace(nets=nets, images=imgs, scales=[float(x) for x in scs[:n_cn]], guess=bool(guess_mode))
-                controlnet, controlnet_image, controlnet_conditioning_scale = None, None, 1.0
-        # controlnet_keep (lora_pipeline.py:421-428): per step, per net, 0.0 or 1.0
-        cn_keep = controlnet_keep(S, control_guidance_start, control_guidance_end, max(1, n_cn))
-        if len(cn_keep[0]) != max(1, n_cn):
-            raise ValueError(f"control_guidance_start / _end must be scalars or hold one entry per ControlNet ({max(1, n_cn)})")
-        # ---- per-request tensors
         stochastic = is_stochastic(self.scheduler, eta)      # omg_fuse_cfg_step_noise + the per-step noise eng.z
-        lats, ehs_l, text_l, masks_l, cehs_l, ctext_l, ip_l, kps_l = [], [], [], [], [], [], [], []
-        z_l, zid_l = [], []                                    # stochastic: per request the (S, 2, C, H, W) noise and what identifies it
-        active = None
+        nets = None if controlnet is None else list(controlnet.nets) if hasattr(controlnet, "nets") else list(controlnet) if isinstance(controlnet, (list, tuple)) else [controlnet]
+        imgs = list(controlnet_image) if isinstance(controlnet_image, (list, tuple)) else [controlnet_image]
+        # ---- 1. per-request tensors
+        t = self._gather_requests(requests, len(lora_list), S, stage, stochastic, height, width, identitynet is not None)
+        # ---- 2. the plan: every decision that needs no device buffer
+        # one batched forward needs ONE UNet behind both pipes (omg_amd.compat shares it; hand-built ConceptModels may not)
+        cm_bank = concept_models.bank if concept_models is not None else None
+        plan = CallPlan(
+            n=n, lora_list=lora_list, S=S, stage=stage, fusion_start=fusion_start, active=t.active, scheduler_cls=type(self.scheduler),
+            stochastic=stochastic, guidance_scale=guidance_scale, use_graph=use_graph, n_nets=None if nets is None else len(nets),
+            cn_image_shapes=[None if im is None else tuple(im.shape) for im in imgs] if nets is not None else (),
+            controlnet_conditioning_scale=controlnet_conditioning_scale, guess_mode=guess_mode, control_guidance_start=control_guidance_start,
+            control_guidance_end=control_guidance_end, has_identitynet=identitynet is not None,
+            identitynet_conditioning_scale=identitynet_conditioning_scale, dedup=dedup, stage_cache=stage_cache is not None, drop_unc0=drop_unc0,
+            concept_shard=concept_shard, has_controller=controller is not None, pure_controller=getattr(controller, "is_pure_replacement", False),
+            callback=callback is not None, callback_steps=callback_steps, callback_on_step_end=callback_on_step_end is not None,
+            callback_on_step_end_tensor_inputs=callback_on_step_end_tensor_inputs, has_concept_models=concept_models is not None,
+            shared=concept_models is None or getattr(concept_models, "_unet", self.unet) is self.unet,
+            bank_adapters=None if cm_bank is None else cm_bank.adapters, bank_mode=None if cm_bank is None else cm_bank.mode, lora_mode=lora_mode,
+            concept_lora=concept_lora, styleL=styleL, main_adapters=main_adapters, concept_adapters=concept_adapters,
+            concept_adapter_scale=concept_adapter_scale, main_scale=(cross_attention_kwargs or {}).get("scale", 1.0))
+        controlnet, cn_nets = (nets[0], None) if plan.use_cn else (None, nets if plan.cn_multi else None)
+        t.cn_image, t.cn_images = (imgs[0], None) if plan.use_cn else (None, imgs if plan.cn_multi else None)
+        bank = cm_bank if plan.use_bank else None
+        if bank is not None and plan.combos:
+            if [tuple(c) for c in plan.combos] != list(bank.slots) or bank.scale != tuple(plan.scales) or bank.mode != lora_mode:
+                bank.build(plan.combos, scale=plan.scales, mode=lora_mode)
+        if plan.twin:      # both samples of every request must be the same computation: [neg0, neg1, pos0, pos1] with equal halves.
+            # ONE fused device comparison and one host sync per call (ADVICE r3: four torch.equal syncs per request before every call)
+            e_all, t_all = torch.stack(t.ehs_l), torch.stack(t.text_l)                   # (n, 4, 77, Cx), (n, 4, P)
+            same = (e_all[:, 0] == e_all[:, 1]).all() & (e_all[:, 2] == e_all[:, 3]).all() & (t_all[:, 0] == t_all[:, 1]).all() & (t_all[:, 2] == t_all[:, 3]).all()
+            plan.twin = bool(same)
+        t.ehs, t.text = torch.cat(t.ehs_l, dim=0).contiguous(), torch.cat(t.text_l, dim=0)          # (4n, 77, Cx), (4n, P)
+        t.tids_main = self._add_time_ids(original_size, crops_coords_top_left, target_size, plan.nm, dev)
+        if negative_original_size is not None and negative_target_size is not None:
+            # lora_pipeline.py:459-474 as executed: cat([negative_add_time_ids, add_time_ids]).repeat(batch_size, 1) -> rows [neg, pos, neg, pos]
+            tids_neg = self._add_time_ids(negative_original_size, negative_crops_coords_top_left, negative_target_size, plan.nm, dev)
+            t.tids_main = torch.where((torch.arange(plan.nm, device=dev) % 2 == 0)[:, None], tids_neg, t.tids_main)
+        t.emb_main = all_step_embeddings(self.unet, t.ts, t.text, t.tids_main)
+        if plan.fuse_possible:
+            t.c_ehs, t.ctext = torch.cat(t.cehs_l, dim=0).contiguous(), torch.cat(t.ctext_l, dim=0)  # (2Ka*n, 77, Cx)
+            t.tids_conc = self._add_time_ids(original_size, crops_coords_top_left, target_size, plan.ncn, dev)
+            t.emb_conc = all_step_embeddings(getattr(concept_models, "_unet", None) or self.unet, t.ts, t.ctext, t.tids_conc)
+        # DDIM's table depends on eta (column 3: the noise coefficient); eta = 0 is the deterministic table, byte for byte
+        t.coef = self.scheduler.coef_table(dev, eta=eta) if isinstance(self.scheduler, DDIMScheduler) else self.scheduler.coef_table(dev)
+        # ---- stage cache: decided in front of the engine because a resumed call without `unc0` runs a different row plan
+        cache_keys: List[str] = []
+        resume = StageCache.Resume()
+        if plan.stage_cache:
+            sizes = (height, width, tuple(original_size),
+                     None if negative_original_size is None or negative_target_size is None else
+                     (tuple(negative_original_size), tuple(negative_crops_coords_top_left), tuple(negative_target_size)),
+                     tuple(crops_coords_top_left), tuple(target_size), str(dt))
+            cache_keys = stage_cache_keys(plan, sizes, self.unet, bank, controller, controlnet, t)
+            resume = stage_cache.lookup(cache_keys, plan, dev, dt)
+        if resume.base_traj is not None:
+            plan = plan.with_drop0()
+        # ---- 3. the persistent engine of this call shape (static buffers + captured step graphs), reused across calls of the same shape
+        Cl, Hl, Wl = t.lats[0].shape[1:]
+        t.mshape = tuple(t.masks_l[0][t.active[0]].shape) if t.active else (0, 0)
+        key = plan.engine_key((str(dt), Cl, Hl, Wl, t.mshape, tuple(t.ehs.shape), id(controller), id(controlnet), id(identitynet),
+                               tuple(id(x) for x in cn_nets or ())))
+        eng = self._engines.pop(key, None)
+        if eng is None:
+            eng = StepEngine(self.unet, plan, t, controller, controlnet, identitynet, cn_nets, concept_models)
+            while len(self._engines) >= self.max_engines:      # least recently used first; its captured graphs go with it
+                self._engines.pop(next(iter(self._engines)))
+                self.engine_evictions += 1
+                if self.engine_evictions in (1, 10, 100):
+                    warnings.warn(f"LoraMultiConceptPipeline: step engine evicted ({self.engine_evictions} so far): more than max_engines="
+                                  f"{self.max_engines} call shapes alternate and each eviction re-captures its hipGraphs; raise pipe.max_engines")
+        self._engines[key] = eng                               # most recently used last
+        # ---- 4. this call's inputs into the engine's buffers, 5. the denoising loop
+        eng.load(plan, t, resume, self.scheduler, concept_models, cross_attention_kwargs, use_graph)
+        for i in range(resume.first, S):
+            eng.run_step(i)
+            if plan.has_cb:
+                self._step_callbacks(eng, i, callback, callback_steps, callback_on_step_end, callback_on_step_end_tensor_inputs)
+            if trajectory is not None:
+                trajectory.append(eng.lat.clone().view(n, 2, Cl, Hl, Wl))
+            if cache_keys and resume.first == 0:
+                stage_cache.store(cache_keys, i, fusion_start, eng.lat, eng.xin, eng.x0_hist if plan.multistep else None)
+        if hasattr(controller, "bind_step_counter"):
+            controller.bind_step_counter(None)      # the counter is the controller's own again (direct UNet calls)
+        return eng.lat.clone().view(n, 2, Cl, Hl, Wl)
+
+    def _gather_requests(self, requests: Sequence[dict], K: int, S: int, stage, stochastic: bool, height: int, width: int,
+                         with_identity: bool) -> SimpleNamespace:
+        """The per-request tensors of a call on the device, one list entry per request, and ``active``: the concepts that have a mask."""
+        dev, dt = self.unet.device, self.unet.dtype
+        t = SimpleNamespace(ts=self.scheduler.timesteps.to(torch.float32), lats=[], ehs_l=[], text_l=[], masks_l=[], cehs_l=[], ctext_l=[], ip_l=[],
+                            kps_l=[], z_l=[], zid_l=[], active=None)      # z_l / zid_l (stochastic): per request the (S, 2, C, H, W) noise and what identifies it
         for r in requests:
             pe, ne = r["prompt_embeds"], r["negative_prompt_embeds"]
             if pe.shape[0] != 2:
                 raise ValueError("prompt_embeds must hold the 2 global prompts [p, p] (lora_pipeline.py:291)")
-            lat0 = self.prepare_latents(1, Cl, height, width, torch.float32, dev, r.get("generator"), r.get("latents"))
-            lats.append(torch.cat([lat0, lat0.clone()]))                                            # duplicated x2 (:409)
+            lat0 = self.prepare_latents(1, self.unet.config.in_channels, height, width, torch.float32, dev, r.get("generator"), r.get("latents"))
+            t.lats.append(torch.cat([lat0, lat0.clone()]))                                            # duplicated x2 (:409)
             if stochastic:      # then one (2, C, H/8, W/8) draw per step, one at a time (a single (S, 2, ...) draw gives other numbers)
                 g = r.get("generator")
                 z_id = g.get_state() if g is not None else None
                 zs = [draw_noise((2,) + tuple(lat0.shape[1:]), g, dev) for _ in range(S)]
-                z_l.append(torch.stack(zs))
-                zid_l.append(z_id if z_id is not None else z_l[-1])
-            ehs_l.append(torch.cat([ne, pe], dim=0).to(device=dev, dtype=dt))                       # CFG order [neg, pos] (:467-474)
-            text_l.append(torch.cat([r["negative_pooled_prompt_embeds"], r["pooled_prompt_embeds"]], dim=0).to(device=dev, dtype=dt))
+                t.z_l.append(torch.stack(zs))
+                t.zid_l.append(z_id if z_id is not None else t.z_l[-1])
+            t.ehs_l.append(torch.cat([ne, pe], dim=0).to(device=dev, dtype=dt))                       # CFG order [neg, pos] (:467-474)
+            t.text_l.append(torch.cat([r["negative_pooled_prompt_embeds"], r["pooled_prompt_embeds"]], dim=0).to(device=dev, dtype=dt))
             rpe = r.get("region_prompt_embeds") or []
             if len(rpe) != K:
                 raise ValueError("one (neg_embeds, pos_embeds, neg_pooled, pos_pooled) tuple per entry of lora_list is required")
@@ -526,630 +1185,41 @@ class LoraMultiConceptPipeline:
                     raise ValueError("stage 2 needs one region mask (or None) per entry of lora_list")
                 masks = [m.to(device=dev, dtype=torch.float32).contiguous() if m is not None else None for m in rm]
             act = [c for c in range(K) if masks[c] is not None]
-            if active is None:
-                active = act
-            elif act != active:
+            if t.active is None:
+                t.active = act
+            elif act != t.active:
                 raise ValueError("requests batched together must have masks for the same concepts")
-            masks_l.append(masks)
+            t.masks_l.append(masks)
             if act:
-                cehs_l.append(torch.cat([torch.cat([rpe[c][0], rpe[c][1]], dim=0) for c in act], dim=0).to(device=dev, dtype=dt))
-                ctext_l.append(torch.cat([torch.cat([rpe[c][2], rpe[c][3]], dim=0) for c in act], dim=0).to(device=dev, dtype=dt))
-                if identitynet is not None:
+                t.cehs_l.append(torch.cat([torch.cat([rpe[c][0], rpe[c][1]], dim=0) for c in act], dim=0).to(device=dev, dtype=dt))
+                t.ctext_l.append(torch.cat([torch.cat([rpe[c][2], rpe[c][3]], dim=0) for c in act], dim=0).to(device=dev, dtype=dt))
+                if with_identity:
                     rie = r.get("region_image_embeds")
                     if rie is None or len(rie) != K or r.get("kps_image") is None:
                         raise ValueError("identitynet needs region_image_embeds [(2,16,Cx)] * K and kps_image per request")
-                    ip_l.append(torch.cat([rie[c] for c in act], dim=0).to(device=dev, dtype=dt))
-                    kps_l.append(r["kps_image"].to(device=dev, dtype=torch.float32))
-        Ka = len(active)
-        shard = concept_shard if (concept_shard is not None and concept_shard.world > 1) else None
-        if shard is not None and stochastic:
-            raise L.OmgHipError("concept_shard with a stochastic step (Euler-ancestral, DDIM eta > 0) is not built: the ranks would have to agree "
-                                "on the noise; run the unsharded call")
-        has_cb = callback is not None or callback_on_step_end is not None
-        if has_cb:
-            if shard is not None:
-                raise L.OmgHipError("callbacks with concept_shard are not built: every rank would have to run the same callback")
-            bad = [k for k in callback_on_step_end_tensor_inputs if k not in _CALLBACK_TENSORS]
-            if bad:
-                raise ValueError(f"callback_on_step_end_tensor_inputs {bad}: only {list(_CALLBACK_TENSORS)} exist (lora_pipeline.py:165)")
-            if callback is not None and (callback_steps is None or int(callback_steps) <= 0):
-                raise ValueError("callback needs a positive callback_steps")
-            dedup, stage_cache, drop_unc0 = False, None, False
-        if cn_multi is not None:
-            if shard is not None:
-                raise L.OmgHipError("concept_shard with a list of ControlNets / guess_mode is not built: run the unsharded call")
-            dedup, stage_cache, drop_unc0 = False, None, False        # the general ControlNet path runs the full batch
-        # a stochastic step gives the two samples of a request different noise from step 0: they are never the same computation
-        twin = bool(dedup) and shard is None and not stochastic and (controller is None or getattr(controller, "is_pure_replacement", False))
-        if twin and controlnet is not None and controlnet_image is not None and controlnet_image.shape[0] not in (1, n):
-            twin = False      # one conditioning image per MAIN ROW (4n): the two samples of a request may differ, and the 2n-row twin batch
-                              # would not divide it — full batch instead
-        if twin:      # both samples of every request must be the same computation: [neg0, neg1, pos0, pos1] with equal halves.
-            # ONE fused device comparison and one host sync per call (ADVICE r3: four torch.equal syncs per request before every call)
-            e_all, t_all = torch.stack(ehs_l), torch.stack(text_l)                   # (n, 4, 77, Cx), (n, 4, P)
-            same = (e_all[:, 0] == e_all[:, 1]).all() & (e_all[:, 2] == e_all[:, 3]).all() & (t_all[:, 0] == t_all[:, 1]).all() & (t_all[:, 2] == t_all[:, 3]).all()
-            twin = bool(same)
-        Hl, Wl = lats[0].shape[2:]
-        fuse_possible = stage == 2 and Ka > 0 and S > fusion_start + 1
-        nm, ncn = 4 * n, 2 * Ka * n                       # rows of the main block / the concept block
-        nb = nm + (ncn if fuse_possible else 0)
-        ehs = torch.cat(ehs_l, dim=0).contiguous()                                                  # (4n, 77, Cx)
-        tids_main = self._add_time_ids(original_size, crops_coords_top_left, target_size, nm, dev)
-        if negative_original_size is not None and negative_target_size is not None:
-            # lora_pipeline.py:459-474 as executed: cat([negative_add_time_ids, add_time_ids]).repeat(batch_size, 1) -> rows [neg, pos, neg, pos]
-            tids_neg = self._add_time_ids(negative_original_size, negative_crops_coords_top_left, negative_target_size, nm, dev)
-            tids_main = torch.where((torch.arange(nm, device=dev) % 2 == 0)[:, None], tids_neg, tids_main)
-        emb_main = self._all_step_embeddings(ts, torch.cat(text_l, dim=0), tids_main)
-        slots: List[int] = []
-        if fuse_possible and concept_models is None:
-            raise ValueError("stage 2 needs concept_models")
-        # ---- LoRA slots.  Concept passes: set_adapters(lora) or set_adapters([lora, "style"], [0.7, 0.5]) (lora_pipeline.py:588-591).
-        # MAIN pass: inference_lora.py:162-164 loads the style LoRA into the main pipe as well, and the main UNet is called with
-        # cross_attention_kwargs={"scale": 0.8} (:546-566), so with styleL every main sample runs with adapter "style" at PEFT
-        # weight 1.0 x scale — one more slot of the same bank, selected for the main rows in plain AND fused steps.
-        # LoRA scale: the concept UNet is always called with cross_attention_kwargs={'scale': 0.8} (hard-coded, :592-598); the main UNet
-        # (style slot) with the caller's cross_attention_kwargs (:546-566; PEFT's default scale is 1.0)
-        main_scale = float((cross_attention_kwargs or {}).get("scale", 1.0))
-        # InstantID's concepts are identities (IP-Adapter tokens + IdentityNet), not LoRA adapters: its `lora_list` only counts them
-        main_adapters = [(str(a), float(w)) for a, w in (main_adapters or ())] or ([("style", 1.0)] if styleL else [])
-        concept_adapters = [(str(a), float(w)) for a, w in (concept_adapters or ())]
-        if concept_lora and concept_adapters:
-            raise ValueError("concept_adapters is the InstantID flow's 'whatever is active' rule; the LoRA flow selects adapters per concept (lora_list)")
-        bank = concept_models.bank if (concept_models is not None and (concept_lora or concept_adapters or main_adapters)) else None
-        combos = []
-        if fuse_possible and concept_lora:
-            combos = [((lora_list[c], 0.7), ("style", 0.5)) if styleL else ((lora_list[c], 1.0),) for c in active]
-        scales = [CONCEPT_LORA_SCALE] * len(combos)
-        if fuse_possible and concept_adapters:              # one combination for every concept row
-            combos, scales = [tuple(concept_adapters)], [float(concept_adapter_scale)]
-        main_slot = -1
-        if main_adapters:
-            if bank is None or any(a not in bank.adapters for a, _ in main_adapters):
-                raise ValueError(f"adapters {[a for a, _ in main_adapters]} on the main pass need concept_models with a LoraBank holding them"
-                                 + (" (styleL=True: the adapter named 'style')" if styleL else ""))
-            main_slot = len(combos)
-            combos = combos + [tuple(main_adapters)]
-            scales.append(main_scale)
-        if concept_adapters and (bank is None or any(a not in bank.adapters for a, _ in concept_adapters)):
-            raise ValueError(f"concept_adapters {[a for a, _ in concept_adapters]} are not in concept_models' LoraBank")
-        if bank is not None and combos:
-            if [tuple(c) for c in combos] != list(bank.slots) or bank.scale != tuple(scales) or bank.mode != lora_mode:
-                bank.build(combos, scale=scales, mode=lora_mode)
-        if fuse_possible:
-            if bank is None or not (concept_lora or concept_adapters):
-                slots = [-1] * ncn
-            elif concept_adapters:
-                slots = [0] * ncn
-            else:
-                slots = [s for _ in range(n) for s in range(Ka) for _ in range(2)]
-            c_ehs = torch.cat(cehs_l, dim=0).contiguous()                                           # (2Ka*n, 77, Cx)
-            emb_conc = self._all_step_embeddings(ts, torch.cat(ctext_l, dim=0),
-                                                 self._add_time_ids(original_size, crops_coords_top_left, target_size, ncn, dev),
-                                                 unet=getattr(concept_models, "_unet", None))
-        merged = bank is not None and bank.mode == "merged"
-        # one batched forward needs ONE UNet behind both pipes (omg_amd.compat shares it; hand-built ConceptModels may not)
-        c_unet = getattr(concept_models, "_unet", self.unet) if concept_models is not None else self.unet
-        shared = c_unet is self.unet
-        batched = fuse_possible and (bank is None or merged) and shared
-        if use_graph and not (bank is None or merged) and (fuse_possible or main_slot >= 0):
-            raise L.OmgHipError("use_graph needs lora_mode='merged' (segment-mode K/V projections are not pointer-stable)")
-        use_cn = controlnet is not None
-        use_idn = identitynet is not None and fuse_possible
-        if use_cn and controlnet_image is None:
-            raise ValueError("controlnet needs controlnet_image")
-        if use_idn and not batched:
-            raise L.OmgHipError("identitynet runs in the batched mode only: merged / no LoRA, and concept_models built on the pipeline's own "
-                                "UNet (omg_amd.compat's from_pretrained shares it between the main and the concept pipe)")
-        if shard is not None and ((fuse_possible and not batched) or use_idn or (controller is not None and not getattr(controller, "is_pure_replacement", False))):
-            raise L.OmgHipError("concept_shard needs the batched step (merged / no LoRA on one shared UNet), a pure-replacement controller and no IdentityNet")
-        mshape = tuple(masks_l[0][active[0]].shape) if active else (0, 0)
-        D = emb_main.shape[-1]
-        # ---- stage cache: everything that determines the latents entering step fusion_start + 1 of request j; decided in
-        # front of the engine because a resumed call without `unc0` runs a different row plan
-        first = 0
-        multistep = isinstance(self.scheduler, DPMSolverMultistepScheduler)    # omg_fuse_cfg_step_ms + the history buffer eng.x0_hist
-        # DDIM's table depends on eta (column 3: the noise coefficient); eta = 0 is the deterministic table, byte for byte
-        coef_now = self.scheduler.coef_table(dev, eta=eta) if isinstance(self.scheduler, DDIMScheduler) else self.scheduler.coef_table(dev)
-        cache_keys: List[str] = []
-        cache_hit = None
-        base_traj = None                      # drop_unc0: per step k the (n, C, H, W) latents / model inputs of the base samples
-        if use_cn and controlnet_image.shape[0] not in (1, n):
-            # one conditioning image per MAIN ROW (4n): the cache key and drop_unc0's compact rows address images per REQUEST — not built for
-            # that layout (the full batch below handles it); neither is used instead of being keyed / indexed wrongly
-            stage_cache, drop_unc0 = None, False
-        if stage_cache is not None and shard is None and S > fusion_start + 1:
-            common = (S, float(guidance_scale), type(self.scheduler).__name__, fusion_start, height, width, tuple(original_size),
-                      None if negative_original_size is None or negative_target_size is None else
-                      (tuple(negative_original_size), tuple(negative_crops_coords_top_left), tuple(negative_target_size)),
-                      tuple(crops_coords_top_left), tuple(target_size), str(dt), tuple(main_adapters), main_scale, lora_mode if main_adapters else None,
-                      id(self.unet), getattr(self.unet, "weights_version", 0), getattr(bank, "version", None) if main_adapters else None,
-                      None if controller is None else (type(controller).__name__, getattr(controller, "is_pure_replacement", False),
-                                                       getattr(controller, "num_self_replace", None)),
-                      None if not use_cn else (id(controlnet), getattr(controlnet, "weights_version", 0), float(controlnet_conditioning_scale),
-                                               tuple(k[0] for k in cn_keep[: fusion_start + 1])))
-            coef_key = coef_now
-            for j in range(n):
-                cn_img = None if not use_cn else (controlnet_image if controlnet_image.shape[0] == 1 else controlnet_image[j: j + 1])
-                z_key = (zid_l[j],) if stochastic else ()        # a trajectory is valid for the same noise only
-                cache_keys.append(StageCache.digest(common, coef_key, lats[j], ehs_l[j], text_l[j], cn_img, *z_key))
-            hit = [stage_cache.get(k) for k in cache_keys]
-            if multistep:      # the first resumed step also reads the data prediction of the step in front of it
-                hist_hit = [stage_cache.get_history(k) for k in cache_keys]
-                hit = [h if m is not None else None for h, m in zip(hit, hist_hit)]
-            if fuse_possible and all(h is not None for h in hit):
-                first, cache_hit = fusion_start + 1, hit                 # every request resumes: the plain steps are not run at all
-                stage_cache.hits += n
-                if drop_unc0 and batched and not use_idn and (controller is None or getattr(controller, "is_pure_replacement", False)):
-                    bases = [stage_cache.get_base(k, first, S) for k in cache_keys]
-                    if all(b is not None for b in bases):
-                        base_traj = {k: (torch.cat([b[k][0] for b in bases]).to(dev), torch.cat([b[k][1] for b in bases]).to(device=dev, dtype=dt))
-                                     for k in range(first + 1, S + 1)}
-            else:
-                stage_cache.misses += n
-        drop0 = base_traj is not None
-        if drop0:      # the compact-row machinery of the concept shard, on ONE rank: main units of three rows [unc1, cond0, cond1]
-            from . import parallel as _par0
-            shard = _par0.ConceptShard(rank=0, world=1)
-            twin = False
-        # ---- persistent engine state (static buffers + captured step graphs), reused across calls of the same shape
-        key = (n, S, Cl, Hl, Wl, K, tuple(active), fuse_possible, fusion_start, type(self.scheduler).__name__, float(guidance_scale),
-               str(dt), batched, bool(styleL), tuple(main_adapters), tuple(concept_adapters), float(concept_adapter_scale), main_scale,
-               tuple(lora_list), mshape, tuple(ehs.shape), id(controller), id(controlnet), id(identitynet),
-               float(controlnet_conditioning_scale), float(identitynet_conditioning_scale), twin,
-               (shard.rank, shard.world) if shard is not None else None, drop0, stochastic,
-               None if cn_multi is None else (tuple(id(x) for x in cn_multi.nets), tuple(tuple(im.shape) for im in cn_multi.images), cn_multi.guess))
-        eng = self._engines.pop(key, None)
-        if eng is not None:
-            self._engines[key] = eng                       # most recently used last
-        if eng is None:
-            eng = SimpleNamespace(graphs={}, warmed=set(), pool=None, coef=None)
-            eng.lat = torch.empty((2 * n, Cl, Hl, Wl), dtype=torch.float32, device=dev)
-            eng.xin = torch.empty((nb, Cl, Hl, Wl), dtype=dt, device=dev)
-            # drop0: the rows of `unc0` are never written — zeros, so that the step kernel's (discarded) update of the base sample stays finite
-            eng.nout = (torch.zeros if drop0 else torch.empty)((nb, Cl, Hl, Wl), dtype=torch.float32, device=dev)
-            eng.step_idx = torch.zeros(1, dtype=torch.int32, device=dev)
-            if multistep:      # the previous step's data prediction of every sample (captured graphs point at it); order-1 steps do not read it
-                eng.x0_hist = torch.zeros((2 * n, Cl, Hl, Wl), dtype=torch.float32, device=dev)
-            if stochastic:     # every step's noise of every sample (captured graphs point at it), refilled in place per call
-                eng.z = torch.empty((S, 2 * n, Cl, Hl, Wl), dtype=torch.float32, device=dev)
-            eng.ehs = torch.empty_like(ehs)
-            eng.emb_main = torch.empty((S, nm, D), dtype=dt, device=dev)
-            eng.emb_cur_main = torch.empty((nm, D), dtype=dt, device=dev)
-            eng.masks = [[torch.empty(mshape, dtype=torch.float32, device=dev) if c in active else None for c in range(K)] for _ in range(n)]
-            if fuse_possible:
-                eng.c_ehs = torch.empty_like(c_ehs)
-                eng.emb_conc = torch.empty((S, ncn, D), dtype=dt, device=dev)
-                eng.emb_cur_conc = torch.empty((ncn, D), dtype=dt, device=dev)
-            if batched:
-                eng.ehs_all = torch.empty((nb,) + tuple(ehs.shape[1:]), dtype=dt, device=dev)
-                eng.emb_all = torch.empty((S, nb, D), dtype=dt, device=dev)
-                eng.emb_cur_all = torch.empty((nb, D), dtype=dt, device=dev)
-            if twin:      # compact rows [unc, cond] per request for the steps in which the two samples coincide
-                eng.xin2 = torch.empty((2 * n, Cl, Hl, Wl), dtype=dt, device=dev)
-                eng.nout2 = torch.empty((2 * n, Cl, Hl, Wl), dtype=torch.float32, device=dev)
-                eng.ehs2 = torch.empty((2 * n,) + tuple(ehs.shape[1:]), dtype=dt, device=dev)
-                eng.emb_main2 = torch.empty((S, 2 * n, D), dtype=dt, device=dev)
-                eng.emb_cur2 = torch.empty((2 * n, D), dtype=dt, device=dev)
-                if use_cn:
-                    eng.cn_emb2 = torch.empty((S, 2 * n, D), dtype=dt, device=dev)
-                    eng.cn_emb_cur2 = torch.empty((2 * n, D), dtype=dt, device=dev)
-            if use_cn:
-                eng.cn_image = torch.empty((controlnet_image.shape[0], 3, height, width), dtype=torch.float32, device=dev)
-                eng.cn_emb = torch.empty((S, nm, D), dtype=dt, device=dev)
-                eng.cn_emb_cur = torch.empty((nm, D), dtype=dt, device=dev)
-            if cn_multi is not None:
-                rows_cn = 2 * n if cn_multi.guess else nm
-                eng.cnm_image = [torch.empty((im.shape[0], 3, height, width), dtype=torch.float32, device=dev) for im in cn_multi.images]
-                eng.cnm_emb = [torch.empty((S, rows_cn, D), dtype=dt, device=dev) for _ in cn_multi.nets]
-                eng.cnm_emb_cur = [torch.empty((rows_cn, D), dtype=dt, device=dev) for _ in cn_multi.nets]
-                if cn_multi.guess:      # the conditional rows [cond0, cond1] of every request, compact
-                    eng.cnm_x = torch.empty((rows_cn, Cl, Hl, Wl), dtype=dt, device=dev)
-                    eng.cnm_ehs = torch.empty((rows_cn,) + tuple(ehs.shape[1:]), dtype=dt, device=dev)
-            if use_idn:
-                eng.ip_all = torch.empty((ncn,) + tuple(ip_l[0].shape[1:]), dtype=dt, device=dev)
-                eng.kps_all = torch.empty((n, 3, height, width), dtype=torch.float32, device=dev)
-                eng.idn_emb = torch.empty((S, ncn, D), dtype=dt, device=dev)
-                eng.idn_emb_cur = torch.empty((ncn, D), dtype=dt, device=dev)
-            if shard is not None:      # per regime (plain / fused): this rank's units, its compact local batch and every rank's row map
-                from . import parallel as _par
-                eng.sh = {}
-                for fz in ((True,) if drop0 else (False, True) if fuse_possible else (False,)):
-                    if drop0:      # every unit on this one rank; a main unit is rows 1..3 of the request's block (`unc0` is not computed)
-                        per_rank = [(list(range(n)), [(j, c) for j in range(n) for c in range(Ka)])]
-                        mrows = [4 * j + r for j in range(n) for r in (1, 2, 3)]
-                        rows = [(mrows + [4 * j + 3 for j, _ in per_rank[0][1] for _ in range(2)],
-                                 mrows + [nm + 2 * Ka * j + 2 * c + r for j, c in per_rank[0][1] for r in range(2)])]
-                    else:
-                        per_rank = _par.assign_units(n, Ka, fz, shard.world)
-                        rows = _par.unit_rows(per_rank, n, Ka)
-                    mains, concs = per_rank[shard.rank]
-                    src, dst = rows[shard.rank]
-                    sh = SimpleNamespace(mains=mains, concs=concs, rows=len(src), n_main=(3 if drop0 else 4) * len(mains), counts=[len(r[1]) for r in rows])
-                    sh.src = torch.tensor(src, dtype=torch.long, device=dev)
-                    sh.dsts = [torch.tensor(r[1], dtype=torch.long, device=dev) for r in rows]
-                    sh.x = torch.empty((sh.rows, Cl, Hl, Wl), dtype=dt, device=dev)
-                    sh.y = torch.zeros((max(sh.counts), Cl, Hl, Wl), dtype=torch.float32, device=dev)
-                    sh.ehs = torch.empty((sh.rows,) + tuple(ehs.shape[1:]), dtype=dt, device=dev)
-                    sh.emb = torch.empty((S, sh.rows, D), dtype=dt, device=dev)
-                    sh.emb_cur = torch.empty((sh.rows, D), dtype=dt, device=dev)
-                    if use_cn and sh.n_main:
-                        sh.cn_emb = torch.empty((S, sh.n_main, D), dtype=dt, device=dev)
-                        sh.cn_emb_cur = torch.empty((sh.n_main, D), dtype=dt, device=dev)
-                        sh.cn_image = torch.empty((len(mains) if controlnet_image.shape[0] != 1 else 1, 3, height, width), dtype=torch.float32, device=dev)
-                    eng.sh[fz] = sh
-            while len(self._engines) >= self.max_engines:      # least recently used first; its captured graphs go with it
-                old_key = next(iter(self._engines))
-                self._engines.pop(old_key)
-                self.engine_evictions += 1
-                if self.engine_evictions in (1, 10, 100):
-                    import warnings
-                    warnings.warn(f"LoraMultiConceptPipeline: step engine evicted ({self.engine_evictions} so far): more than max_engines="
-                                  f"{self.max_engines} call shapes alternate and each eviction re-captures its hipGraphs; raise pipe.max_engines")
-            self._engines[key] = eng
-            # the key holds id()s: keep the objects alive so that an id cannot be recycled for a different object
-            eng.refs = (controller, controlnet, identitynet, concept_models, cn_multi.nets if cn_multi is not None else None)
-            eng.epoch = pointer_epoch()
-        # ---- load this call's inputs into the static buffers (device-to-device copies; graphs keep their pointers)
-        lat = eng.lat
-        lat.copy_(torch.cat(lats, dim=0))
-        eng.ehs.copy_(ehs)
-        eng.emb_main.copy_(emb_main)
-        # coef_now (above), per call: the key holds the scheduler's class and step count, not its
-        if eng.coef is None:                               # configuration — a re-configured scheduler must not meet a cached table
-            eng.coef = coef_now.clone()                    # the engine's OWN buffer: the scheduler's cached table is shared and read-only
-        else:
-            eng.coef.copy_(coef_now)                       # in place: captured graphs keep the pointer
-        eng.step_idx.zero_()
-        if stochastic:
-            for j in range(n):
-                eng.z[:, 2 * j: 2 * j + 2].copy_(z_l[j])
-        for j in range(n):
-            for c in active:
-                eng.masks[j][c].copy_(masks_l[j][c])
-        xin, nout, step_idx, coef = eng.xin, eng.nout, eng.step_idx, eng.coef
-        if cache_hit is not None:                                        # resume (decided in front of the engine, above)
-            lat.copy_(torch.cat([h.to(dev) for h in cache_hit], dim=0))
-            if multistep:
-                eng.x0_hist.copy_(torch.cat([h.to(dev) for h in hist_hit], dim=0))
-            step_idx.fill_(first)
-            if controller is not None:
-                controller.cur_step = first                              # the host-side counters the skipped steps would have ticked
-        cin0 = self.scheduler.cin0(dev) if first == 0 else torch.tensor([self.scheduler.cin[first]], dtype=torch.float32, device=dev)
-        for j in range(n):
-            ops.scale_model_input(lat[2 * j: 2 * j + 2], cin0, xin[4 * j: 4 * j + 4])
-        main_kw = dict(cross_attention_kwargs or {})
-        main_kw.pop("scale", None)
-        main_kw["omg_main_batch"] = 4
-        main_kw["omg_images"] = n
-        if fuse_possible:
-            eng.c_ehs.copy_(c_ehs)
-            eng.emb_conc.copy_(emb_conc)
-        if batched:
-            eng.ehs_all[:nm].copy_(ehs)
-            eng.ehs_all[nm:].copy_(c_ehs)
-            eng.emb_all[:, :nm].copy_(emb_main)
-            eng.emb_all[:, nm:].copy_(emb_conc)
-            state_all = concept_models.lora_state([main_slot + 1] * nm + [s + 1 for s in slots], merged=True) if bank is not None else None
-        # main-only forwards (plain steps; the main half of un-batched fused steps): base weights, or the style slot
-        state_main = None
-        if main_slot >= 0:
-            state_main = concept_models.lora_state([main_slot + 1] * nm, merged=True) if merged else concept_models.lora_state([main_slot] * nm, merged=False)
-        tids_m = tids_main
-        if use_cn:
-            eng.cn_image.copy_(controlnet_image.to(device=dev, dtype=torch.float32))
-            t_all = ts.reshape(S, 1).expand(S, nm).reshape(-1).contiguous()
-            eng.cn_emb.copy_(controlnet.time_embed(t_all, S * nm, torch.cat(text_l, dim=0).repeat(S, 1), tids_m.repeat(S, 1)).view(S, nm, D))
-        if cn_multi is not None:
-            cond_rows = torch.tensor([4 * j + r for j in range(n) for r in (2, 3)], dtype=torch.long, device=dev)
-            text_cn, tids_cn, rows_cn = torch.cat(text_l, dim=0), tids_m, nm
-            if cn_multi.guess:      # add_text_embeds.chunk(2)[1] / add_time_ids.chunk(2)[1] / prompt_embeds.chunk(2)[1] (lora_pipeline.py:497-503)
-                text_cn, tids_cn, rows_cn = text_cn.index_select(0, cond_rows), tids_m.index_select(0, cond_rows), 2 * n
-                eng.cnm_ehs.copy_(ehs.index_select(0, cond_rows))
-            t_all = ts.reshape(S, 1).expand(S, rows_cn).reshape(-1).contiguous()
-            for k_, net in enumerate(cn_multi.nets):
-                eng.cnm_image[k_].copy_(cn_multi.images[k_].to(device=dev, dtype=torch.float32))
-                eng.cnm_emb[k_].copy_(net.time_embed(t_all, S * rows_cn, text_cn.repeat(S, 1), tids_cn.repeat(S, 1)).view(S, rows_cn, D))
-                if use_graph:
-                    net.refresh_cross_kv(eng.cnm_ehs if cn_multi.guess else eng.ehs)
-                    net.cond_features(eng.cnm_image[k_])
-        if use_idn:
-            eng.ip_all.copy_(torch.cat(ip_l, dim=0))
-            eng.kps_all.copy_(torch.cat(kps_l, dim=0))
-            t_all = ts.reshape(S, 1).expand(S, ncn).reshape(-1).contiguous()
-            tids_c = self._add_time_ids(original_size, crops_coords_top_left, target_size, ncn, dev)
-            eng.idn_emb.copy_(identitynet.time_embed(t_all, S * ncn, torch.cat(ctext_l, dim=0).repeat(S, 1), tids_c.repeat(S, 1)).view(S, ncn, D))
-        state_twin = None
-        if twin:
-            rows2 = torch.tensor([4 * j + r for j in range(n) for r in (0, 2)], dtype=torch.long, device=dev)      # unc0, cond0 of each request
-            eng.ehs2.copy_(ehs.index_select(0, rows2))
-            eng.emb_main2.copy_(emb_main.index_select(1, rows2))
-            if use_cn:
-                eng.cn_emb2.copy_(eng.cn_emb.index_select(1, rows2))
-            if main_slot >= 0:
-                state_twin = concept_models.lora_state([main_slot + 1] * (2 * n), merged=True) if merged else concept_models.lora_state([main_slot] * (2 * n), merged=False)
-        if shard is not None:
-            for fz, sh in eng.sh.items():
-                if not sh.rows:
-                    continue
-                src_e, src_m = (eng.ehs_all, eng.emb_all) if fz else (eng.ehs, eng.emb_main)
-                sh.ehs.copy_(src_e.index_select(0, sh.dsts[shard.rank]))
-                sh.emb.copy_(src_m.index_select(1, sh.dsts[shard.rank]))
-                sh.state = None
-                if bank is not None and (main_slot >= 0 or sh.concs):
-                    sh.state = concept_models.lora_state([main_slot + 1] * sh.n_main + [jj + 1 for _, jj in sh.concs for _ in range(2)], merged=True)
-                if use_cn and sh.n_main:
-                    sh.cn_emb.copy_(eng.cn_emb.index_select(1, sh.dsts[shard.rank][: sh.n_main]))
-                    sh.cn_image.copy_(eng.cn_image if eng.cn_image.shape[0] == 1 else eng.cn_image[sh.mains])
-                if use_graph:
-                    self.unet.refresh_cross_kv(sh.ehs, sh.state)
-                    if use_cn and sh.n_main:
-                        controlnet.refresh_cross_kv(sh.ehs[: sh.n_main])
-                        controlnet.cond_features(sh.cn_image)
-        if use_graph and shard is None:
-            # cached cross-attention K/V (and ControlNet conditioning features) must be refreshed eagerly:
-            # replayed graphs read the stored tensors
-            if twin:
-                self.unet.refresh_cross_kv(eng.ehs2, state_twin)
-                if use_cn:
-                    controlnet.refresh_cross_kv(eng.ehs2)
-            self.unet.refresh_cross_kv(eng.ehs, state_main)
-            if batched:
-                self.unet.refresh_cross_kv(eng.ehs_all, state_all)
-            if use_cn:
-                controlnet.refresh_cross_kv(eng.ehs)
-                controlnet.cond_features(eng.cn_image)
-            if use_idn:
-                identitynet.refresh_cross_kv(eng.ip_all)
-                identitynet.cond_features(eng.kps_all)
-                self.unet.refresh_ip_kv(eng.ip_all)      # the UNet's own image-prompt K / V^T of the concept samples
+                    t.ip_l.append(torch.cat([rie[c] for c in act], dim=0).to(device=dev, dtype=dt))
+                    t.kps_l.append(r["kps_image"].to(device=dev, dtype=torch.float32))
+        return t
 
-        # the conditioning scales of the CURRENT step (host floats baked into the zero convolutions' epilogues, hence part of the graph regime):
-        # scale * controlnet_keep[i] (lora_pipeline.py:511-517; instantid_pipeline.py:566-578: the one window scales the IdentityNet and the t2i net)
-        cur = SimpleNamespace(cn=float(controlnet_conditioning_scale), idn=float(identitynet_conditioning_scale), multi=())
-
-        def set_step_scales(i: int) -> tuple:
-            k0 = cn_keep[i][0]
-            cur.cn, cur.idn = float(controlnet_conditioning_scale) * k0, float(identitynet_conditioning_scale) * k0
-            if cn_multi is not None:
-                cur.multi = tuple(sc * cn_keep[i][k_] for k_, sc in enumerate(cn_multi.scales))
-            return (cur.cn if use_cn else None, cur.idn if use_idn else None, cur.multi)
-
-        def multi_residuals():
-            """The general ControlNet block of a step: every net of the list on the main rows (guess_mode: on the conditional rows only), residuals
-            summed in list order like MultiControlNetModel.forward — first the nets' residuals among themselves, then onto the skips — and, in
-            guess_mode, no residual for the unconditional rows (lora_pipeline.py:531-535 concatenates zeros)."""
-            sum_d = sum_m = None
-            if cn_multi.guess:
-                eng.cnm_x.view(n, 2, Cl, Hl, Wl).copy_(xin[:nm].view(n, 4, Cl, Hl, Wl)[:, 2:4])
-            for k_, net in enumerate(cn_multi.nets):
-                sc = cur.multi[k_]
-                if sc == 0.0:
-                    continue
-                ops.gather_step(eng.cnm_emb[k_], step_idx, eng.cnm_emb_cur[k_])
-                d_, m_ = net(eng.cnm_x if cn_multi.guess else xin[:nm], None, encoder_hidden_states=eng.cnm_ehs if cn_multi.guess else eng.ehs,
-                             controlnet_cond=eng.cnm_image[k_], conditioning_scale=sc, emb=eng.cnm_emb_cur[k_], guess_mode=cn_multi.guess)
-                if sum_d is None:
-                    sum_d, sum_m = d_, m_
-                else:
-                    for a_, b_ in zip(sum_d + [sum_m], d_ + [m_]):
-                        ops.add_(a_.permute(0, 2, 3, 1), b_.permute(0, 2, 3, 1))
-            if sum_d is None:
-                return []
-            if not cn_multi.guess:
-                return [(0, nm, sum_d, sum_m)]
-            return [(4 * j + 2, 4 * j + 4, [d_[2 * j: 2 * j + 2] for d_ in sum_d], sum_m[2 * j: 2 * j + 2]) for j in range(n)]
-
-        def region_rows(j):
-            return nm + 2 * Ka * j
-
-        def fill_region_inputs():
-            for j in range(n):                            # latent_model_input[3:4] duplicated (:583-585), per request
-                r0 = region_rows(j)
-                xin[r0: r0 + 2 * Ka].copy_(xin[4 * j + 3: 4 * j + 4].expand(2 * Ka, -1, -1, -1))
-
-        def twin_body():
-            """A step in which samples 0 and 1 of every request are still identical: one [unc, cond] forward per request, the noise
-            prediction written to both samples, then the ordinary CFG + scheduler step on all four rows."""
-            kw = dict(main_kw)
-            kw["omg_twin"] = True
-            x2, y2 = eng.xin2, eng.nout2
-            x2.view(n, 2, Cl, Hl, Wl).copy_(xin[:nm].view(n, 2, 2, Cl, Hl, Wl)[:, :, 0])
-            if use_cn and cur.cn != 0.0:
-                ops.gather_step(eng.cn_emb2, step_idx, eng.cn_emb_cur2)
-                d_, m_ = controlnet(x2, None, encoder_hidden_states=eng.ehs2, controlnet_cond=eng.cn_image,
-                                    conditioning_scale=cur.cn, emb=eng.cn_emb_cur2)
-                kw["omg_residuals"] = [(0, 2 * n, d_, m_)]
-            ops.gather_step(eng.emb_main2, step_idx, eng.emb_cur2)
-            self.unet.set_lora_state(state_twin)
-            try:
-                self.unet(x2, None, encoder_hidden_states=eng.ehs2, cross_attention_kwargs=kw, emb=eng.emb_cur2, out=y2)
-            finally:
-                self.unet.set_lora_state(None)
-            nout[:nm].view(n, 2, 2, Cl, Hl, Wl).copy_(y2.view(n, 2, 1, Cl, Hl, Wl).expand(n, 2, 2, Cl, Hl, Wl))
-            for j in range(n):
-                scheduler_step(j, fuse=False, region_preds=[None] * K, masks=[None] * K, advance=(j == n - 1))
-
-        def step_body(fused: bool, twin_step: bool = False):
-            """One denoising iteration; every per-step quantity is selected by the DEVICE step counter."""
-            if twin_step:
-                return twin_body()
-            kw = dict(main_kw)
-            residuals = []
-            if use_cn and cur.cn != 0.0:                  # ControlNet on the main samples (lora_pipeline.py:519-536); scale 0 = outside its guidance window
-                ops.gather_step(eng.cn_emb, step_idx, eng.cn_emb_cur)
-                d_, m_ = controlnet(xin[:nm], None, encoder_hidden_states=eng.ehs, controlnet_cond=eng.cn_image,
-                                    conditioning_scale=cur.cn, emb=eng.cn_emb_cur)
-                residuals.append((0, nm, d_, m_))
-            if cn_multi is not None:
-                residuals.extend(multi_residuals())
-            if fused and batched:
-                fill_region_inputs()
-                if use_idn:                               # IdentityNet on the concept samples (instantid_pipeline.py:638-648)
-                    if cur.idn != 0.0:
-                        ops.gather_step(eng.idn_emb, step_idx, eng.idn_emb_cur)
-                        d_, m_ = identitynet(xin[nm:], None, encoder_hidden_states=eng.ip_all, controlnet_cond=eng.kps_all,
-                                             conditioning_scale=cur.idn, emb=eng.idn_emb_cur)
-                        residuals.append((nm, nb, d_, m_))
-                    kw["omg_ip_tokens"], kw["omg_ip_rows"] = eng.ip_all, nm
-                if residuals:
-                    kw["omg_residuals"] = residuals
-                ops.gather_step(eng.emb_all, step_idx, eng.emb_cur_all)
-                self.unet.set_lora_state(state_all)
-                try:
-                    self.unet(xin, None, encoder_hidden_states=eng.ehs_all, cross_attention_kwargs=kw, emb=eng.emb_cur_all, out=nout)
-                finally:
-                    self.unet.set_lora_state(None)
-            else:
-                if residuals:
-                    kw["omg_residuals"] = residuals
-                ops.gather_step(eng.emb_main, step_idx, eng.emb_cur_main)
-                self.unet.set_lora_state(state_main)
-                try:
-                    self.unet(xin[:nm], None, encoder_hidden_states=eng.ehs, cross_attention_kwargs=kw, emb=eng.emb_cur_main, out=nout[:nm])
-                finally:
-                    self.unet.set_lora_state(None)
-                if fused:
-                    fill_region_inputs()
-                    ops.gather_step(eng.emb_conc, step_idx, eng.emb_cur_conc)
-                    concept_models.unet_batched(xin[nm:], None, eng.c_ehs, slots, emb=eng.emb_cur_conc, out=nout[nm:])
-            finish(fused)
-
-        def finish(fused: bool):
-            """Region fusion + CFG + scheduler update + next model input of every request (one launch each)."""
-            for j in range(n):
-                regs: List[Optional[torch.Tensor]] = [None] * K
-                if fused:
-                    for jj, c in enumerate(active):
-                        r0 = region_rows(j) + 2 * jj
-                        regs[c] = nout[r0: r0 + 2]
-                scheduler_step(j, fuse=fused, region_preds=regs, masks=eng.masks[j] if fused else [None] * K, advance=(j == n - 1))
-
-        def scheduler_step(j: int, **kw):
-            """request j's fusion + CFG + scheduler update + next model input: the one-step linear table (DDIM, Euler) or the
-            multistep one with the request's rows of the history buffer (DPM-Solver++), or the one-step table plus the request's
-            noise (Euler-ancestral, DDIM eta > 0)"""
-            if stochastic:
-                ops.fuse_cfg_step_noise(nout[4 * j: 4 * j + 4], lat[2 * j: 2 * j + 2], coef, eng.z[:, 2 * j: 2 * j + 2], step_idx,
-                                        guidance_scale=guidance_scale, model_input_next=xin[4 * j: 4 * j + 4], **kw)
-            elif multistep:
-                ops.fuse_cfg_step_ms(nout[4 * j: 4 * j + 4], lat[2 * j: 2 * j + 2], coef, eng.x0_hist[2 * j: 2 * j + 2], step_idx,
-                                     guidance_scale=guidance_scale, model_input_next=xin[4 * j: 4 * j + 4], **kw)
-            else:
-                ops.fuse_cfg_step(nout[4 * j: 4 * j + 4], lat[2 * j: 2 * j + 2], coef, step_idx, guidance_scale=guidance_scale,
-                                  model_input_next=xin[4 * j: 4 * j + 4], **kw)
-
-        def shard_forward(fused: bool, _tw: bool = False):
-            """This rank's units of the step: main blocks first, then concept pairs, as one compact batch."""
-            sh = eng.sh[fused]
-            kw = dict(main_kw)
-            kw["omg_images"] = len(sh.mains)
-            if drop0:
-                kw["omg_main_batch"] = 3                  # [unc1, cond0, cond1]: cond1 borrows Q, K of cond0 = row 1 of the block
-            sh.x.copy_(xin[:nm].index_select(0, sh.src))
-            if use_cn and sh.n_main and cur.cn != 0.0:
-                ops.gather_step(sh.cn_emb, step_idx, sh.cn_emb_cur)
-                d_, m_ = controlnet(sh.x[: sh.n_main], None, encoder_hidden_states=sh.ehs[: sh.n_main], controlnet_cond=sh.cn_image,
-                                    conditioning_scale=cur.cn, emb=sh.cn_emb_cur)
-                kw["omg_residuals"] = [(0, sh.n_main, d_, m_)]
-            ops.gather_step(sh.emb, step_idx, sh.emb_cur)
-            self.unet.set_lora_state(sh.state)
-            try:
-                self.unet(sh.x, None, encoder_hidden_states=sh.ehs, cross_attention_kwargs=kw, emb=sh.emb_cur, out=sh.y[: sh.rows])
-            finally:
-                self.unet.set_lora_state(None)
-
-        def run_step(i: int):
-            fused = fuse_possible and i > fusion_start
-            tw = twin and not fused          # the samples part ways at the first fused step (stage 1: never)
-            scales_i = set_step_scales(i)
-            if shard is not None:
-                sh = eng.sh[fused]
-                if sh.rows:
-                    run_forward(shard_forward, fused, False, ("shard", fused, scales_i))
-                elif controller is not None:
-                    controller.cur_step += 1          # no unit of this step is ours: only the host-side step counter moves
-                shard.exchange(sh.y, sh.counts, sh.dsts, nout)
-                finish(fused)
-                if drop0:      # the base samples were not computed: their latents and next model inputs are the stage-1 call's
-                    bl, bx = base_traj[i + 1]
-                    lat.view(n, 2, Cl, Hl, Wl)[:, 0].copy_(bl)
-                    if i + 1 < S:
-                        xin[:nm].view(n, 4, Cl, Hl, Wl)[:, 2].copy_(bx)
-                return
-            run_forward(step_body, fused, tw, (fused, scales_i))
-
-        def run_forward(body, fused: bool, tw: bool, tag: tuple):
-            if not use_graph:
-                body(fused, tw)
-                return
-            if eng.epoch != pointer_epoch():          # a weight image or cached K/V the graphs point at was freed or re-allocated
-                eng.graphs.clear()
-                eng.warmed.clear()
-                eng.pool = None                       # the pool dies with its last graph: a later capture must open a new one
-                eng.epoch = pointer_epoch()
-            win = controller._self_window() if controller is not None and hasattr(controller, "_self_window") else None
-            # the cross edit's kind at this step ("borrow" / "own" / "mixed": different launches); WITHIN a kind one graph serves every
-            # step, because the edit's alpha row is selected on the device through the step counter bound below (+ its host offset)
-            ck = (controller.cross_kind(), ctl_step_offset) if hasattr(controller, "cross_kind") else None
-            regime = tag + (win, tw, ck)
-            g = eng.graphs.get(regime)
-            if g is not None:
-                g.replay()
-                if controller is not None:
-                    controller.cur_step += 1          # the replayed graph does not run the host-side counters
-                return
-            if regime not in eng.warmed:              # first step of a regime runs eagerly (lazy inits, caches)
-                body(fused, tw)
-                eng.warmed.add(regime)
-                return
-            g = torch.cuda.CUDAGraph()
-            torch.cuda.synchronize()
-            with torch.cuda.graph(g, pool=eng.pool):
-                body(fused, tw)                       # records the step; host counters tick as in eager mode
-            if eng.pool is None:
-                eng.pool = g.pool()
-            eng.graphs[regime] = g
-            g.replay()
-
-        # the general prompt-to-prompt edit reads alpha[cur_step] on the device: cur_step == step_idx + offset from here to the end of the
-        # call (a resumed call set cur_step = first above; replays advance the host counter by one per step, as step_idx advances)
-        ctl_step_offset = 0
-        if hasattr(controller, "bind_step_counter"):
-            ctl_step_offset = controller.cur_step - first
-            controller.bind_step_counter(step_idx, ctl_step_offset)
-        # ---- 8. denoising loop
-        for i in range(first, S):
-            run_step(i)
-            if has_cb:
-                t_i = self.scheduler.timesteps[i]
-                for j in range(n):
-                    lj = lat[2 * j: 2 * j + 2]
-                    if callback_on_step_end is not None:
-                        avail = {"latents": lj, "prompt_embeds": eng.ehs[4 * j: 4 * j + 4], "negative_prompt_embeds": eng.ehs[4 * j: 4 * j + 2]}
-                        outs = dict(callback_on_step_end(self, i, t_i, {k: avail[k] for k in callback_on_step_end_tensor_inputs}) or {})
-                        new = outs.pop("latents", lj)
-                        for k_, v_ in outs.items():
-                            if k_ in avail and v_ is not avail[k_] and not torch.equal(v_.to(avail[k_]), avail[k_]):
-                                raise L.OmgHipError(f"callback_on_step_end returned a new {k_}: only `latents` can be replaced mid-loop")
-                        if new is not lj:
-                            lj.copy_(new.to(device=dev, dtype=torch.float32))
-                            if i + 1 < S:      # the step kernel wrote the next model input from ITS latents: redo it from the callback's
-                                ops.scale_model_input(lj, torch.tensor([self.scheduler.cin[i + 1]], dtype=torch.float32, device=dev), xin[4 * j: 4 * j + 4])
-                    if callback is not None and i % int(callback_steps) == 0:
-                        callback(i // getattr(self.scheduler, "order", 1), t_i, lj)
-            if trajectory is not None:
-                trajectory.append(lat.clone().view(n, 2, Cl, Hl, Wl))
-            if cache_keys and first == 0 and i == fusion_start:         # the latents entering the first fused step of a stage-2 call
-                for j, k in enumerate(cache_keys):
-                    stage_cache.put(k, lat[2 * j: 2 * j + 2])
-                    if multistep:                                       # ... and the data prediction that step reads besides them
-                        stage_cache.put_history(k, eng.x0_hist[2 * j: 2 * j + 2])
-            if cache_keys and first == 0 and i >= fusion_start:         # ... and the base sample's way from there on (drop_unc0)
-                for j, k in enumerate(cache_keys):
-                    stage_cache.put_base(k, i + 1, lat[2 * j: 2 * j + 1], xin[4 * j + 2: 4 * j + 3])
-        if hasattr(controller, "bind_step_counter"):
-            controller.bind_step_counter(None)      # the counter is the controller's own again (direct UNet calls)
-        return lat.clone().view(n, 2, Cl, Hl, Wl)
+    def _step_callbacks(self, eng: "StepEngine", i: int, callback, callback_steps, callback_on_step_end, tensor_inputs) -> None:
+        """The reference's callbacks after step i (lora_pipeline.py:617-632), once per request; see ``generate_many``."""
+        t_i = self.scheduler.timesteps[i]
+        ehs = eng.main.ehs
+        for j in range(eng.plan.n):
+            lj = eng.lat[2 * j: 2 * j + 2]
+            if callback_on_step_end is not None:
+                avail = {"latents": lj, "prompt_embeds": ehs[4 * j: 4 * j + 4], "negative_prompt_embeds": ehs[4 * j: 4 * j + 2]}
+                outs = dict(callback_on_step_end(self, i, t_i, {k: avail[k] for k in tensor_inputs}) or {})
+                new = outs.pop("latents", lj)
+                for k_, v_ in outs.items():
+                    if k_ in avail and v_ is not avail[k_] and not torch.equal(v_.to(avail[k_]), avail[k_]):
+                        raise L.OmgHipError(f"callback_on_step_end returned a new {k_}: only `latents` can be replaced mid-loop")
+                if new is not lj:
+                    lj.copy_(new.to(device=lj.device, dtype=torch.float32))
+                    if i + 1 < eng.plan.S:      # the step kernel wrote the next model input from ITS latents: redo it from the callback's
+                        ops.scale_model_input(lj, torch.tensor([self.scheduler.cin[i + 1]], dtype=torch.float32, device=lj.device), eng.xin[4 * j: 4 * j + 4])
+            if callback is not None and i % int(callback_steps) == 0:
+                callback(i // getattr(self.scheduler, "order", 1), t_i, lj)
 
 
 class InstantidMultiConceptPipeline(LoraMultiConceptPipeline):

@@ -272,3 +272,84 @@ def test_controlnet_keep_is_the_reference_s_schedule():
     assert controlnet_keep(4, [0.0, 0.25], 0.5) == [[1.0, 0.0], [1.0, 1.0], [0.0, 0.0], [0.0, 0.0]]
     with pytest.raises(ValueError):
         controlnet_keep(4, [0.0, 0.1], [1.0])
+
+
+def _plan(**kw):
+    """CallPlan on plain values: K = 2 concepts, n = 2 requests, S = 20, fusion_start = 15, a bank holding the concepts and a style adapter"""
+    from omg_amd.pipeline import CallPlan
+    base = dict(n=2, lora_list=["c0", "c1"], S=20, stage=2, fusion_start=15, active=[0, 1],
+                bank_adapters={"c0": None, "c1": None, "style": None}, bank_mode="merged")
+    base.update(kw)
+    return CallPlan(**base)
+
+
+def test_call_plan_row_counts_and_lora_slots():
+    """Which rows a step of generate_many runs and which LoRA slot each gets — decided on plain values before any device buffer exists."""
+    p = _plan()                                                    # the LoRA flow: one slot per concept, base weights on the main rows
+    assert (p.nm, p.ncn, p.nb, p.Ka, p.fuse_possible, p.batched) == (8, 8, 16, 2, True, True)
+    assert p.combos == [(("c0", 1.0),), (("c1", 1.0),)] and p.scales == [0.8, 0.8] and p.main_slot == -1
+    assert p.slots == [0, 0, 1, 1, 0, 0, 1, 1]
+    p = _plan(styleL=True, main_scale=0.6)                         # + style: [concept, "style"] at 0.7 / 0.5, and one more slot for the main rows
+    assert p.combos == [(("c0", 0.7), ("style", 0.5)), (("c1", 0.7), ("style", 0.5)), (("style", 1.0),)]
+    assert p.scales == [0.8, 0.8, 0.6] and p.main_slot == 2 and p.slots == [0, 0, 1, 1, 0, 0, 1, 1]
+    p = _plan(concept_lora=False, concept_adapters=[("style", 1.0)], concept_adapter_scale=0.9)      # InstantID's "whatever is active"
+    assert p.combos == [(("style", 1.0),)] and p.scales == [0.9] and p.slots == [0] * 8 and p.main_slot == -1
+    p = _plan(bank_adapters=None, bank_mode=None)
+    assert not p.use_bank and p.slots == [-1] * 8 and p.main_slot == -1 and not p.merged and p.batched
+    p = _plan(stage=1, active=[])                                  # stage 1 never fuses
+    assert not p.fuse_possible and p.nb == p.nm == 8 and p.slots == [] and not p.batched
+    p = _plan(lora_mode="segment")                                 # segment-mode LoRA: the concept rows run as their own forward
+    assert not p.merged and not p.batched
+
+
+def test_call_plan_fall_backs_to_the_full_batch():
+    """dedup / stage_cache / drop_unc0 are used only where they are exact; everywhere else the call silently runs the full batch."""
+    from omg_amd.schedulers import EulerAncestralDiscreteScheduler, is_stochastic
+    on = dict(dedup=True, stage_cache=True, drop_unc0=True)
+    p = _plan(**on)
+    assert (p.twin, p.stage_cache, p.drop_unc0) == (True, True, True)
+    for off in (dict(callback=True, callback_steps=1), dict(callback_on_step_end=True),
+                dict(n_nets=2, cn_image_shapes=[(1, 3, 64, 64)] * 2, controlnet_conditioning_scale=[1.0, 0.5]),
+                dict(n_nets=1, cn_image_shapes=[(1, 3, 64, 64)], guess_mode=True)):
+        p = _plan(**on, **off)
+        assert (p.twin, p.stage_cache, p.drop_unc0) == (False, False, False), off
+    p = _plan(**on, n_nets=1, cn_image_shapes=[(2, 3, 64, 64)], controlnet_conditioning_scale=0.5)      # one image per request: all stay on
+    assert p.use_cn and not p.cn_multi and p.cn_scale == 0.5 and (p.twin, p.stage_cache, p.drop_unc0) == (True, True, True)
+    p = _plan(**on, n_nets=1, cn_image_shapes=[(8, 3, 64, 64)])                                           # one image per MAIN ROW
+    assert (p.twin, p.stage_cache, p.drop_unc0) == (False, False, False)
+    sched = EulerAncestralDiscreteScheduler
+    p = _plan(**on, scheduler_cls=sched, stochastic=is_stochastic(sched(), 0.0))
+    assert p.stochastic and not p.twin and p.stage_cache
+    p = _plan(**on, has_controller=True, pure_controller=False)      # a general prompt-to-prompt edit tells the two samples apart
+    assert not p.twin and not p.drop_unc0 and p.stage_cache
+    assert _plan(**on, has_controller=True, pure_controller=True).twin
+
+
+def test_call_plan_refusals():
+    from omg_amd import _lib as L
+    shard = parallel.ConceptShard(rank=1, world=2)
+    for err, match, kw in (
+            (L.OmgHipError, "concept_shard with a stochastic step", dict(concept_shard=shard, stochastic=True)),
+            (L.OmgHipError, "callbacks with concept_shard", dict(concept_shard=shard, callback_on_step_end=True)),
+            (L.OmgHipError, "use_graph needs lora_mode='merged'", dict(use_graph=True, lora_mode="segment")),
+            (L.OmgHipError, "identitynet runs in the batched mode only", dict(has_identitynet=True, lora_mode="segment")),
+            (L.OmgHipError, "identitynet runs in the batched mode only", dict(has_identitynet=True, shared=False)),
+            (ValueError, "concept_adapters is the InstantID flow", dict(concept_adapters=[("style", 1.0)])),
+            (ValueError, "2 ControlNet\\(s\\) need as many conditioning images and scales",
+             dict(n_nets=2, cn_image_shapes=[(1, 3, 64, 64)], controlnet_conditioning_scale=[1.0, 1.0])),
+            (ValueError, "2 ControlNet\\(s\\) need as many conditioning images and scales",
+             dict(n_nets=2, cn_image_shapes=[(1, 3, 64, 64)] * 2, controlnet_conditioning_scale=[1.0]))):
+        with pytest.raises(err, match=match):
+            _plan(**kw)
+
+
+def test_engine_key_tells_row_plans_apart():
+    """twin, drop0, a stochastic step and the shard rank each change the engine's buffers or launches: none may share an engine"""
+    p = _plan(dedup=True)
+    variants = [p, p.replace(twin=False), p.with_drop0(), p.replace(stochastic=True),
+                p.replace(shard=parallel.ConceptShard(rank=0, world=2)),
+                p.replace(shard=parallel.ConceptShard(rank=1, world=2))]
+    assert p.with_drop0().drop0 and not p.with_drop0().twin and p.with_drop0().shard.world == 1
+    keys = [v.engine_key() for v in variants]
+    assert len(set(keys)) == len(keys)
+    assert _plan(dedup=True).engine_key() == p.engine_key()
