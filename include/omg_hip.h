@@ -716,6 +716,44 @@ int omg_attn_masked(int dtype, int B, int heads, int Nq, int Nk, const void* Q, 
                     const void* K, int64_t ldk, int64_t k_bstride, const void* V, int64_t ldv, int64_t v_bstride,
                     const uint8_t* mask, float scale, void* O, int64_t ldo, int64_t o_bstride, void* stream);
 
+/* ------------------------------------------------------------------------
+ * GroundingDINO's query selection, decoder and heads (omg_amd/gdino_decoder.py: transformers' GroundingDinoModel.forward from "prepare
+ * decoder inputs" on, GroundingDinoDecoder and the head loop of GroundingDinoForObjectDetection).  The rules of the block above hold.
+ *
+ * omg_attn_hd32: O [B Nq][ldo] = softmax(scale Q K^T under key_mask) V per head at head_dim 32, any Nq, Nk >= 1; key_mask [B Nk] bytes
+ *   (the same for every query and head) or NULL.  The decoder's self-attention (no mask) and its text cross-attention (the padded-token
+ *   mask; the library adds finfo.min to padded keys, which is the same thing except for an all-excluded row: undefined and finite
+ *   here).  Operands as omg_attn_masked: rows of ld* elements, samples *_bstride apart, head h at column 32 h — a column slice of a fused
+ *   projection buffer is an operand.  The tiled kernel of the block above at D = 32: one 16x16x32 MFMA step per 16-key tile.
+ *
+ * omg_msdeform_attn_box: omg_msdeform_attn with box reference points, ref [B Nq L 4] fp32 (cx, cy, w, h) per sampled level (16-byte
+ *   aligned): loc = (cx, cy) + off / 4 (w, h) 0.5; pixel x = loc_x W_l - 0.5, FORMED AS fma(cx, W_l, fma(off_x, s, -0.5)) with
+ *   s = w (W_l / 8) rounded once (W_l / 8 is exact), y alike with h and H_l.  Everything else — lanes, taps, summation order, the value
+ *   mask, the clamp of far-out coordinates, the checks — is omg_msdeform_attn's.
+ *
+ * omg_gdino_contrastive: GroundingDinoContrastiveEmbedding.  S[b, n, t] = X[b, n, :] . Y[b, t, :] over 256 channels, X [B N][ldx],
+ *   Y [B T][ldy], 1 <= T <= max_text_len <= 256 (a multiple of 4), text_mask [B T] bytes.  16-bit MFMA operands, fp32 accumulation,
+ *   stored without a rounding to 16 bits.  logits [B, N, max_text_len] fp32 or NULL: masked tokens and columns T .. max_text_len - 1
+ *   hold -inf.  rowmax [B, N] fp32 or NULL: bitwise the maximum of what logits holds.  At least one of the two.
+ *
+ * omg_gdino_ref_step: the reference bookkeeping of one decoder layer, one launch.  rows = B Q.
+ *   base  = logit_in [rows 4] (may hold +inf) if given, else torch.special.logit(ref_in [rows 4], eps = 1e-5); exactly one of the two.
+ *   Hd [rows][ldh] (the box head's second hidden state, 256 wide) with W3 [4, 256], b3 [4], or NULL:
+ *     Hd given:  ref_out = sigmoid(W3 Hd + b3 + base), the product in fp32, never rounded to 16 bits;
+ *     Hd NULL:   ref_out = ref_in as it is (the step in front of layer 0), or sigmoid(logit_in).
+ *   ref_input [rows L 4] fp32 or NULL = ref_out times (vx, vy, vx, vy) of valid_ratios [B L 2] per level.
+ *   emb [rows][lde] (storage type, 512 wide) or NULL = encode_sinusoidal_position_embedding(ref_input[:, 0, :], 128): blocks y, x, w, h.
+ * ---------------------------------------------------------------------- */
+int omg_attn_hd32(int dtype, int B, int heads, int Nq, int Nk, const void* Q, int64_t ldq, int64_t q_bstride,
+                  const void* K, int64_t ldk, int64_t k_bstride, const void* V, int64_t ldv, int64_t v_bstride,
+                  const uint8_t* key_mask, float scale, void* O, int64_t ldo, int64_t o_bstride, void* stream);
+int omg_msdeform_attn_box(const omg_msdeform_args* a, void* stream);
+int omg_gdino_contrastive(int dtype, int B, int N, int T, int max_text_len, const void* X, int64_t ldx, const void* Y, int64_t ldy,
+                          const uint8_t* text_mask, float* logits, float* rowmax, void* stream);
+int omg_gdino_ref_step(int dtype, int B, int Q, int L, const float* ref_in, const float* logit_in, const float* valid_ratios,
+                       const void* Hd, int64_t ldh, const void* W3, const void* b3, float* ref_out, float* ref_input,
+                       void* emb, int64_t lde, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,8 @@ _SEGMENT_ANYTHING = ("Sam", "SamPredictor", "ResizeLongestSide", "build_sam", "b
 _DPT = ("DPTForDepthEstimation", "DPTImageProcessor", "DPTFeatureExtractor", "depth_condition")
 _SWIN = ("SwinBackbone", "swin_from_groundingdino")
 _GDINO = ("GroundingDinoEncoder", "GroundingDinoEncoderOutput")
-__all__ = list(_SAM) + list(_SAM_VIT) + list(_SEGMENT_ANYTHING) + list(_DPT) + list(_SWIN) + list(_GDINO)
+_GDINO_DECODER = ("GroundingDinoDecoderHead", "GroundingDinoDetectionOutput", "GroundingDinoDetector")
+__all__ = list(_SAM) + list(_SAM_VIT) + list(_SEGMENT_ANYTHING) + list(_DPT) + list(_SWIN) + list(_GDINO) + list(_GDINO_DECODER)
 
 
 def __getattr__(name):          # the segmenter's public names, imported on first use (omg_amd.sam pulls in torch and the kernels' bindings)
@@ -31,4 +32,7 @@ def __getattr__(name):          # the segmenter's public names, imported on firs
     if name in _GDINO:
         from . import gdino
         return getattr(gdino, name)
+    if name in _GDINO_DECODER:
+        from . import gdino_decoder
+        return getattr(gdino_decoder, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

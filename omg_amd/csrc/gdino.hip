@@ -9,6 +9,11 @@
 //                         chunks across workgroups, fp32 partials (maximum, sum, accumulator) in the workspace, a second launch folds
 //                         them in chunk order.
 //   omg_attn_masked       softmax attention at head_dim 64 under a byte mask [B, Nq, Nk] (the text enhancer's self-attention).
+// and, for the decoder behind it (omg_amd/gdino_decoder.py; its other kernels are in gdino_decoder.hip), the same two bodies again:
+//   omg_msdeform_attn_box msdeform_body with BOX reference points [B, Nq, L, 4] (cx, cy, w, h).
+//   omg_attn_hd32         attn_tiled_body at head_dim 32 under a key mask [B, Nk]: any Nq, Nk.
+// A body is a device function and every entry a kernel of its own name (msdeform_kernel / msdeform_box_kernel, attn_tiled_kernel /
+// attn_hd32_kernel), so the enhancer's kernels are the instances they were.
 //
 // msdeform_kernel.  FOUR lanes are one (query, head): lane `sub` owns channels 8 sub .. 8 sub + 7 of the head's 32, so a tap is one
 // 16-byte load per lane and the four lanes read one 64-byte row piece.  Every lane forms the softmax and the locations of its (query,
@@ -50,15 +55,15 @@ struct MsdP {
   const char* value; long ldv;           // [B N][ldv]
   const unsigned char* mask;             // [B N], 0: the row reads as zeros; or null
   const char* ow; long ldow;             // [B Nq][ldow]: offsets (head, level, point, xy) | logits (head, level point)
-  const float* ref;                      // [B Nq L 2] (x, y)
+  const float* ref;                      // [B Nq L 2] (x, y); BOX: [B Nq L 4] (cx, cy, w, h)
   char* out; long ldo;                   // [B Nq][ldo]
   int N, Nq, heads;
   long pairs;                            // B Nq heads
   int H[4], W[4], start[4];
 };
 
-template <typename T, int L, bool MASK>
-__global__ __launch_bounds__(256) void msdeform_kernel(MsdP p) {
+template <typename T, int L, bool MASK, bool BOX>
+OMG_DEV void msdeform_body(const MsdP& p) {
   constexpr int P = 4;
   using V4 = typename Vec<T>::v4;
   const int sub = threadIdx.x & 3;
@@ -99,15 +104,24 @@ __global__ __launch_bounds__(256) void msdeform_kernel(MsdP p) {
     float off[8];
     load8<T>(owr + ((long)h * L * P * 2 + l * P * 2) * 2, off);
     const V4 lg = *(const V4*)(lgp + l * P * 2);
-    const float rx = p.ref[(row * L + l) * 2], ry = p.ref[(row * L + l) * 2 + 1];
+    float rx, ry, sx = 0.f, sy = 0.f;
+    if (BOX) {
+      // box reference (cx, cy, w, h): loc = c + off / 4 * (w, h) * 0.5, pixel x = cx W + off_x (w W / 8) - 0.5.  The step per unit of
+      // offset, s = w (W / 8), is ONE rounding (W / 8 is exact); the coordinate is fma(cx, W, fma(off, s, -0.5)): two more.
+      const f32x4 r4 = *(const f32x4*)(p.ref + (row * L + l) * 4);
+      rx = r4[0]; ry = r4[1];
+      sx = r4[2] * ((float)Wl * 0.125f); sy = r4[3] * ((float)Hl * 0.125f);
+    } else {
+      rx = p.ref[(row * L + l) * 2]; ry = p.ref[(row * L + l) * 2 + 1];
+    }
     u32x4 raw[P * 4];
     float wt[P * 4];
 #pragma unroll
     for (int i = 0; i < P; ++i) {
       // pixel coordinate of loc = ref + off / (W, H) under align_corners = False: loc W - 0.5.  Beyond [-2, n + 1] every corner is
       // outside whatever the value, so the clamp changes no result and keeps the conversion to int defined (a NaN takes the bound).
-      float x = __builtin_fmaf(rx, (float)Wl, off[2 * i] - 0.5f);
-      float y = __builtin_fmaf(ry, (float)Hl, off[2 * i + 1] - 0.5f);
+      float x = __builtin_fmaf(rx, (float)Wl, BOX ? __builtin_fmaf(off[2 * i], sx, -0.5f) : off[2 * i] - 0.5f);
+      float y = __builtin_fmaf(ry, (float)Hl, BOX ? __builtin_fmaf(off[2 * i + 1], sy, -0.5f) : off[2 * i + 1] - 0.5f);
       x = fminf(fmaxf(x, -2.0f), (float)Wl + 1.0f);
       y = fminf(fmaxf(y, -2.0f), (float)Hl + 1.0f);
       const float xf = floorf(x), yf = floorf(y);
@@ -138,6 +152,12 @@ __global__ __launch_bounds__(256) void msdeform_kernel(MsdP p) {
   store8<T>(p.out + (row * p.ldo + (long)h * 32 + sub * 8) * 2, acc);
 }
 
+// the two entries are kernels of their own names: point references [B Nq L 2] and box references [B Nq L 4]
+template <typename T, int L, bool MASK>
+__global__ __launch_bounds__(256) void msdeform_kernel(MsdP p) { msdeform_body<T, L, MASK, false>(p); }
+template <typename T, int L, bool MASK>
+__global__ __launch_bounds__(256) void msdeform_box_kernel(MsdP p) { msdeform_body<T, L, MASK, true>(p); }
+
 // ------------------------------------------------------------------ tiled attention
 struct AtP {
   const char *q, *k, *v;                 // rows of ld* elements, samples q/k/v_bs elements apart; head h at column h D
@@ -150,7 +170,7 @@ struct AtP {
 };
 
 template <typename T, int D, bool MASK2D, bool PARTIAL>
-__global__ __launch_bounds__(256) void attn_tiled_kernel(AtP p) {
+OMG_DEV void attn_tiled_body(const AtP& p) {
   constexpr int KT = 64;                       // keys per LDS tile
   constexpr int KSTR = D * 2 + 16;             // K row, bytes: sixteen consecutive rows start on different 16-byte slots
   constexpr int VSTR = KT * 2 + 16;            // V^T row, bytes
@@ -293,6 +313,13 @@ __global__ __launch_bounds__(256) void attn_tiled_kernel(AtP p) {
   }
 }
 
+template <typename T, int D, bool MASK2D, bool PARTIAL>
+__global__ __launch_bounds__(256) void attn_tiled_kernel(AtP p) { attn_tiled_body<T, D, MASK2D, PARTIAL>(p); }
+// head_dim 32 under a key mask [B Nk] (the decoder's self-attention and text cross-attention): one 16x16x32 step per 16-key tile, two
+// accumulator blocks
+template <typename T>
+__global__ __launch_bounds__(256) void attn_hd32_kernel(AtP p) { attn_tiled_body<T, 32, false, false>(p); }
+
 // ---- thread = (sample, head, row, 4 channels): the chunks' partials in ascending order
 template <typename T, int D>
 __global__ __launch_bounds__(256) void attn_fold_kernel(const float* ws, char* out, long ldo, long o_bs, int B, int heads, int Nq, int nchunks) {
@@ -329,20 +356,25 @@ __global__ __launch_bounds__(256) void attn_fold_kernel(const float* ws, char* o
 bool gd_aligned16(const void* p) { return (uintptr_t)p % 16 == 0; }
 
 template <typename T, int L>
-int msd_launch(const MsdP& p, bool mask, hipStream_t s) {
+int msd_launch(const MsdP& p, bool mask, bool box, hipStream_t s) {
   const dim3 grid((unsigned)((p.pairs + 63) / 64));
-  if (mask) OMG_LAUNCH((msdeform_kernel<T, L, true>), grid, dim3(256), 0, s, p);
-  else OMG_LAUNCH((msdeform_kernel<T, L, false>), grid, dim3(256), 0, s, p);
+  if (box) {
+    if (mask) OMG_LAUNCH((msdeform_box_kernel<T, L, true>), grid, dim3(256), 0, s, p);
+    else OMG_LAUNCH((msdeform_box_kernel<T, L, false>), grid, dim3(256), 0, s, p);
+  } else {
+    if (mask) OMG_LAUNCH((msdeform_kernel<T, L, true>), grid, dim3(256), 0, s, p);
+    else OMG_LAUNCH((msdeform_kernel<T, L, false>), grid, dim3(256), 0, s, p);
+  }
   return omg_check_launch("msdeform_attn");
 }
 
 template <typename T>
-int msd_dispatch(const MsdP& p, int L, bool mask, hipStream_t s) {
+int msd_dispatch(const MsdP& p, int L, bool mask, bool box, hipStream_t s) {
   switch (L) {
-    case 1: return msd_launch<T, 1>(p, mask, s);
-    case 2: return msd_launch<T, 2>(p, mask, s);
-    case 3: return msd_launch<T, 3>(p, mask, s);
-    default: return msd_launch<T, 4>(p, mask, s);
+    case 1: return msd_launch<T, 1>(p, mask, box, s);
+    case 2: return msd_launch<T, 2>(p, mask, box, s);
+    case 3: return msd_launch<T, 3>(p, mask, box, s);
+    default: return msd_launch<T, 4>(p, mask, box, s);
   }
 }
 
@@ -373,9 +405,8 @@ int bi_check(const char* what, int dtype, int B, int heads, int N, int T, const 
   return 0;
 }
 
-}  // namespace
-
-extern "C" int omg_msdeform_attn(const omg_msdeform_args* a, void* stream) {
+// omg_msdeform_attn (box = false) and omg_msdeform_attn_box: one set of checks
+int msd_entry(const omg_msdeform_args* a, void* stream, bool box) {
   OMG_REQUIRE(a != nullptr, "omg_msdeform_attn: null args");
   OMG_REQUIRE(a->dtype == OMG_F16 || a->dtype == OMG_BF16, "omg_msdeform_attn: dtype");
   OMG_REQUIRE(a->head_dim == 32, "omg_msdeform_attn: head_dim 32");
@@ -393,7 +424,7 @@ extern "C" int omg_msdeform_attn(const omg_msdeform_args* a, void* stream) {
   OMG_REQUIRE(a->ldv >= hd && a->ldo >= hd && a->ldow >= (int64_t)a->heads * a->L * 12,
               "omg_msdeform_attn: row stride below heads 32 (value, out) / heads L 12 (offsets | logits)");
   OMG_REQUIRE(a->ldv % 8 == 0 && a->ldo % 8 == 0 && a->ldow % 8 == 0, "omg_msdeform_attn: row strides multiples of 8");
-  OMG_REQUIRE(gd_aligned16(a->value) && gd_aligned16(a->ow) && gd_aligned16(a->out) && (uintptr_t)a->ref % 4 == 0,
+  OMG_REQUIRE(gd_aligned16(a->value) && gd_aligned16(a->ow) && gd_aligned16(a->out) && (uintptr_t)a->ref % (box ? 16 : 4) == 0,
               "omg_msdeform_attn: 16-byte aligned operands");
   MsdP p;
   p.value = (const char*)a->value; p.ldv = (long)a->ldv;
@@ -407,7 +438,41 @@ extern "C" int omg_msdeform_attn(const omg_msdeform_args* a, void* stream) {
     p.H[l] = l < a->L ? a->H[l] : 1; p.W[l] = l < a->L ? a->W[l] : 1; p.start[l] = l < a->L ? a->start[l] : 0;
   }
   hipStream_t s = (hipStream_t)stream;
-  return a->dtype == OMG_F16 ? msd_dispatch<f16>(p, a->L, a->mask != nullptr, s) : msd_dispatch<bf16>(p, a->L, a->mask != nullptr, s);
+  return a->dtype == OMG_F16 ? msd_dispatch<f16>(p, a->L, a->mask != nullptr, box, s) : msd_dispatch<bf16>(p, a->L, a->mask != nullptr, box, s);
+}
+
+}  // namespace
+
+extern "C" int omg_msdeform_attn(const omg_msdeform_args* a, void* stream) { return msd_entry(a, stream, false); }
+extern "C" int omg_msdeform_attn_box(const omg_msdeform_args* a, void* stream) { return msd_entry(a, stream, true); }
+
+extern "C" int omg_attn_hd32(int dtype, int B, int heads, int Nq, int Nk, const void* Q, int64_t ldq, int64_t q_bstride,
+                             const void* K, int64_t ldk, int64_t k_bstride, const void* V, int64_t ldv, int64_t v_bstride,
+                             const uint8_t* key_mask, float scale, void* O, int64_t ldo, int64_t o_bstride, void* stream) {
+  OMG_REQUIRE(dtype == OMG_F16 || dtype == OMG_BF16, "omg_attn_hd32: dtype");
+  OMG_REQUIRE(B >= 0 && Nq >= 0 && Nk >= 0 && heads >= 1, "omg_attn_hd32: B, Nq, Nk >= 0, heads >= 1");
+  OMG_REQUIRE(B <= 65535 && heads <= 65535 && Nq <= (1 << 24) && Nk <= (1 << 24), "omg_attn_hd32: B, heads at most 65535, Nq, Nk at most 2^24");
+  if (B == 0 || Nq == 0 || Nk == 0) return OMG_OK;
+  OMG_REQUIRE(Q && K && V && O, "omg_attn_hd32: null operand");
+  const int64_t hd = (int64_t)heads * 32;
+  OMG_REQUIRE(ldq >= hd && ldk >= hd && ldv >= hd && ldo >= hd, "omg_attn_hd32: row stride below heads 32");
+  OMG_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0 && q_bstride % 8 == 0 && k_bstride % 8 == 0 &&
+              v_bstride % 8 == 0 && o_bstride % 8 == 0, "omg_attn_hd32: row and batch strides multiples of 8");
+  OMG_REQUIRE(gd_aligned16(Q) && gd_aligned16(K) && gd_aligned16(V) && gd_aligned16(O), "omg_attn_hd32: 16-byte aligned operands");
+  AtP p;
+  p.q = (const char*)Q; p.ldq = (long)ldq; p.q_bs = (long)q_bstride;
+  p.k = (const char*)K; p.ldk = (long)ldk; p.k_bs = (long)k_bstride;
+  p.v = (const char*)V; p.ldv = (long)ldv; p.v_bs = (long)v_bstride;
+  p.mask = key_mask;
+  p.out = (char*)O; p.ldo = (long)ldo; p.o_bs = (long)o_bstride;
+  p.ws = nullptr;
+  p.heads = heads; p.Nq = Nq; p.Nk = Nk; p.chunk = Nk; p.nchunks = 1;
+  p.scale_log2e = scale * GD_LOG2E;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)((Nq + 63) / 64), (unsigned)heads, (unsigned)B);
+  if (dtype == OMG_F16) OMG_LAUNCH((attn_hd32_kernel<f16>), grid, dim3(256), 0, s, p);
+  else OMG_LAUNCH((attn_hd32_kernel<bf16>), grid, dim3(256), 0, s, p);
+  return omg_check_launch("attn_hd32");
 }
 
 extern "C" int omg_attn_bi_vision(int dtype, int B, int heads, int N, int T, const void* vis, int64_t ld_vis, int64_t vis_bstride,

@@ -989,6 +989,18 @@ def msdeform_attn(value: torch.Tensor, ow: torch.Tensor, ref: torch.Tensor, spat
     is a multiple of 8 is fine), ``ow`` [B, Nq, heads*L*12] = sampling_offsets | attention_weights of the queries, ``ref`` [B, Nq, L, 2]
     fp32 (x, y), ``spatial_shapes`` [(H_l, W_l)] with level l at rows ``level_start[l]`` (default: one after the other), ``mask`` [B, N]
     bool / uint8, 0 = the value row reads as zeros -> [B, Nq, heads*32].  omg_msdeform_attn."""
+    return _msdeform(value, ow, ref, spatial_shapes, heads, points, mask, level_start, out, 2)
+
+
+def msdeform_attn_box(value: torch.Tensor, ow: torch.Tensor, ref: torch.Tensor, spatial_shapes: Sequence[Tuple[int, int]], *, heads: int = 8,
+                      points: int = 4, mask: Optional[torch.Tensor] = None, level_start: Optional[Sequence[int]] = None,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`msdeform_attn` with box reference points ``ref`` [B, Nq, L, 4] fp32 (cx, cy, w, h) per sampled level (the decoder's
+    ``reference_points_input``): a point's location is ``(cx, cy) + off / 4 * (w, h) * 0.5``.  omg_msdeform_attn_box."""
+    return _msdeform(value, ow, ref, spatial_shapes, heads, points, mask, level_start, out, 4)
+
+
+def _msdeform(value, ow, ref, spatial_shapes, heads, points, mask, level_start, out, coords):
     _dev(value)
     B, N, Wd = value.shape
     Nq = ow.shape[1]
@@ -997,7 +1009,7 @@ def msdeform_attn(value: torch.Tensor, ow: torch.Tensor, ref: torch.Tensor, spat
         raise L.OmgHipError(f"msdeform_attn: {Lv} levels; the kernel takes 1 to 4")
     assert Wd % heads == 0 and value.stride(2) == 1 and (B == 1 or value.stride(0) == N * value.stride(1))
     assert ow.shape == (B, Nq, heads * Lv * points * 3) and ow.stride(2) == 1 and (B == 1 or ow.stride(0) == Nq * ow.stride(1)) and ow.dtype == value.dtype
-    assert ref.shape == (B, Nq, Lv, 2) and ref.dtype == torch.float32 and ref.is_contiguous() and ref.is_cuda
+    assert ref.shape == (B, Nq, Lv, coords) and ref.dtype == torch.float32 and ref.is_contiguous() and ref.is_cuda
     mask = _bytes(mask, (B, N), value.device)
     if level_start is None:
         level_start, s = [], 0
@@ -1016,7 +1028,10 @@ def msdeform_attn(value: torch.Tensor, ow: torch.Tensor, ref: torch.Tensor, spat
     a.ow, a.ldow, a.ref = ow.data_ptr(), ow.stride(1), ref.data_ptr()
     a.out, a.ldo = out.data_ptr(), out.stride(1)
     t0 = _PROF.begin() if _PROF is not None else None
-    L.check(L.lib().omg_msdeform_attn(C.byref(a), _stream()), "omg_msdeform_attn")
+    if coords == 4:
+        L.check(L.lib().omg_msdeform_attn_box(C.byref(a), _stream()), "omg_msdeform_attn_box")
+    else:
+        L.check(L.lib().omg_msdeform_attn(C.byref(a), _stream()), "omg_msdeform_attn")
     if _PROF is not None:
         _PROF.end("msdeform_attn", 2.0 * B * Nq * Wd * Lv * points * 4, t0, ("msdeform_attn", Nq, N, Lv))
     return out
@@ -1092,6 +1107,79 @@ def attn_masked(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, s
                                     v.data_ptr(), v.stride(1), v.stride(0), _p(mask), scale, out.data_ptr(), out.stride(1), out.stride(0),
                                     _stream()), "omg_attn_masked")
     return out
+
+
+def attn_hd32(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: float, *, key_mask: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``softmax(q k^T scale under key_mask) v`` per head at head_dim 32: ``q`` [B, Nq, heads*32], ``k`` / ``v`` [B, Nk, heads*32], any Nq,
+    Nk >= 1, ``key_mask`` [B, Nk] bool / uint8 (1 = attend) -> [B, Nq, heads*32].  Column slices of a projection buffer are fine.
+    omg_attn_hd32."""
+    _dev(q)
+    B, Nq, Wd = q.shape
+    Nk = k.shape[1]
+    assert Wd == heads * 32 and k.shape == (B, Nk, Wd) and v.shape == (B, Nk, Wd) and k.dtype == q.dtype and v.dtype == q.dtype
+    assert q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1
+    key_mask = _bytes(key_mask, (B, Nk), q.device)
+    if out is None:
+        out = torch.empty((B, Nq, Wd), dtype=q.dtype, device=q.device)
+    assert out.shape == (B, Nq, Wd) and out.stride(2) == 1 and out.dtype == q.dtype
+    t0 = _PROF.begin() if _PROF is not None else None
+    L.check(L.lib().omg_attn_hd32(_dt(q), B, heads, Nq, Nk, q.data_ptr(), q.stride(1), q.stride(0), k.data_ptr(), k.stride(1), k.stride(0),
+                                  v.data_ptr(), v.stride(1), v.stride(0), _p(key_mask), scale, out.data_ptr(), out.stride(1), out.stride(0),
+                                  _stream()), "omg_attn_hd32")
+    if _PROF is not None:
+        _PROF.end("attn_hd32", 4.0 * B * Nq * Nk * Wd, t0, ("attn_hd32", Nq, Nk))
+    return out
+
+
+def gdino_contrastive(x: torch.Tensor, y: torch.Tensor, text_mask: torch.Tensor, max_text_len: int = 256, *, logits: bool = True,
+                      rowmax: bool = False):
+    """GroundingDinoContrastiveEmbedding: ``x`` [B, N, 256], ``y`` [B, T, 256] (row strides multiples of 8), ``text_mask`` [B, T] bool /
+    uint8 -> the fp32 logits [B, N, max_text_len] (-inf on masked tokens and beyond T), their row maximum [B, N], or (logits, rowmax) —
+    whichever of the two is asked for; with ``logits=False`` no [B, N, T] tensor is written.  omg_gdino_contrastive."""
+    _dev(x)
+    B, N, Wd = x.shape
+    T = y.shape[1]
+    assert Wd == 256 and y.shape == (B, T, 256) and y.dtype == x.dtype and x.stride(2) == 1 and y.stride(2) == 1
+    assert (B == 1 or x.stride(0) == N * x.stride(1)) and (B == 1 or y.stride(0) == T * y.stride(1))
+    assert logits or rowmax
+    text_mask = _bytes(text_mask, (B, T), x.device)
+    lg = torch.empty((B, N, max_text_len), dtype=torch.float32, device=x.device) if logits else None
+    rm = torch.empty((B, N), dtype=torch.float32, device=x.device) if rowmax else None
+    t0 = _PROF.begin() if _PROF is not None else None
+    L.check(L.lib().omg_gdino_contrastive(_dt(x), B, N, T, int(max_text_len), x.data_ptr(), x.stride(1), y.data_ptr(), y.stride(1),
+                                          _p(text_mask), _p(lg), _p(rm), _stream()), "omg_gdino_contrastive")
+    if _PROF is not None:
+        _PROF.end("gdino_contrastive", 2.0 * B * N * T * 256, t0, ("gdino_contrastive", N, T))
+    return (lg, rm) if logits and rowmax else (lg if logits else rm)
+
+
+def gdino_ref_step(valid_ratios: torch.Tensor, *, ref_in: Optional[torch.Tensor] = None, logit_in: Optional[torch.Tensor] = None,
+                   hidden: Optional[torch.Tensor] = None, w3: Optional[torch.Tensor] = None, b3: Optional[torch.Tensor] = None,
+                   dtype: Optional[torch.dtype] = None, embed: bool = True):
+    """One decoder layer's reference bookkeeping.  ``ref_in`` [B, Q, 4] fp32 (its ``torch.special.logit(eps=1e-5)`` is the base) or
+    ``logit_in`` [B, Q, 4] fp32 (the base itself, +inf allowed); ``hidden`` [B, Q, 256] (the box head's second hidden state, 16-bit) with
+    the head's last Linear ``w3`` [4, 256], ``b3`` [4], or None (``ref_out = ref_in`` / ``sigmoid(logit_in)``); ``valid_ratios`` [B, L, 2]
+    fp32 -> (ref_out [B, Q, 4], ref_input [B, Q, L, 4], embedding [B, Q, 512] in the storage type or None).  omg_gdino_ref_step."""
+    base = ref_in if ref_in is not None else logit_in
+    assert base is not None and (ref_in is None or logit_in is None)
+    _dev(base)
+    B, Q, _ = base.shape
+    Lv = valid_ratios.shape[1]
+    assert base.shape == (B, Q, 4) and base.dtype == torch.float32 and base.is_contiguous()
+    assert valid_ratios.shape == (B, Lv, 2) and valid_ratios.dtype == torch.float32 and valid_ratios.is_contiguous() and valid_ratios.is_cuda
+    if hidden is not None:
+        assert hidden.shape == (B, Q, 256) and hidden.stride(2) == 1 and (B == 1 or hidden.stride(0) == Q * hidden.stride(1))
+        assert w3.shape == (4, 256) and b3.shape == (4,) and w3.dtype == hidden.dtype and b3.dtype == hidden.dtype and w3.is_contiguous()
+        dtype = hidden.dtype
+    assert dtype in (torch.float16, torch.bfloat16)
+    ref_out = torch.empty((B, Q, 4), dtype=torch.float32, device=base.device)
+    ref_input = torch.empty((B, Q, Lv, 4), dtype=torch.float32, device=base.device)
+    emb = torch.empty((B, Q, 512), dtype=dtype, device=base.device) if embed else None
+    L.check(L.lib().omg_gdino_ref_step(L.OMG_F16 if dtype == torch.float16 else L.OMG_BF16, B, Q, Lv, _p(ref_in), _p(logit_in),
+                                       valid_ratios.data_ptr(), _p(hidden), hidden.stride(1) if hidden is not None else 0, _p(w3), _p(b3),
+                                       ref_out.data_ptr(), ref_input.data_ptr(), _p(emb), 512, _stream()), "omg_gdino_ref_step")
+    return ref_out, ref_input, emb
 
 
 def conv3x3_nhwc_ex(x: torch.Tensor, w: torch.Tensor, *, stride: int = 1, bias: Optional[torch.Tensor] = None, act: int = 0,
