@@ -754,6 +754,44 @@ int omg_gdino_ref_step(int dtype, int B, int Q, int L, const float* ref_in, cons
                        const void* Hd, int64_t ldh, const void* W3, const void* b3, float* ref_out, float* ref_input,
                        void* emb, int64_t lde, void* stream);
 
+/* ------------------------------------------------------------------------
+ * GroundingDINO's BERT text encoder (omg_amd/bert.py: transformers' BertModel without its pooler).  Attention is omg_attn_masked on
+ * column slices of the fused q | k | v rows, LayerNorms omg_layernorm.  Storage fp16 / bf16, arithmetic fp32, one rounding at the store;
+ * no atomics, no workspace; every reduction order is fixed by the operand's own sizes.
+ *
+ * omg_gemm_skinny: C[M, N] = epi(A[M, K] W[N, K]^T) for FEW rows (a caption is 6 to 30 tokens): the launch is a stream of W, so the
+ *   work is cut along N and never along M.
+ *   A [M][lda], W [N][ldw] (torch Linear layout), C [M][ldc], residual [M][ldr]: row strides in ELEMENTS, multiples of 8 and at least
+ *     the row's length, base pointers 16-byte aligned — a column slice of a wider buffer is an operand.  K % 8 == 0, N % 8 == 0 (the
+ *     rules of omg_gemm), any M >= 1.
+ *   epi, in this order: + bias [N] (or NULL); gelu = 1: the erf GELU of omg_gelu_erf (gelu.h, not a tanh form); + residual (or NULL),
+ *     added AFTER the activation.  Products on the 16-bit MFMA (16x16x32), sums and the epilogue in fp32, ONE rounding at the store.
+ *   Work split: a workgroup owns 8 columns of N (16 from N = 2048 on) over the WHOLE of K, so every workgroup streams its own rows of
+ *     W exactly once and nothing is reduced across workgroups: no atomics, no workspace, no second launch.  K is cut into steps of 64
+ *     elements; wave w of the workgroup's four takes the steps w, w + 4, w + 8, ... in ascending order and the four fp32 partial tiles
+ *     are added through LDS in ascending wave order.  The split is a function of K alone.  Up to 64 rows share one pass over the
+ *     workgroup's weights; further rows are a second grid dimension (their weights come from L2).
+ *   Invariance: the bits of row r of C depend on row r of A, on W and on row r of the epilogue operands — not on M, not on r's position
+ *     in the call, not on what other rows hold (Inf and NaN included), not on the column slice width.
+ *   Nothing outside an operand is read: a K tail (a multiple of 8, not of 64), an N tail narrower than a slice and the rows that pad M
+ *     to the MFMA tile are read from a clamped address inside the operand and replaced by zeros in registers.
+ *   Refused with a message: dtype, NULL A / W / C, M, N or K < 1, K or N not a multiple of 8, a stride that is not a multiple of 8 or
+ *     shorter than its row, a misaligned base, gelu other than 0 / 1, M beyond 64 * 65535.
+ *
+ * omg_bert_embed_ln: BertEmbeddings.forward for inference, one launch.  Per token t of M:
+ *     Y[t] = LayerNorm(word[input_ids[t]] + type[token_type_ids[t]] + pos[position_ids[t]]) * gamma + beta
+ *   the sum formed in that order in fp32, two-pass fp32 statistics over the row in registers (omg_layernorm's), eps a float (BERT's is
+ *   1e-12), one rounding to the storage type.  The ids are the int64 tensors torch holds, read on the device: no cast pass, no host
+ *   synchronisation.  word [n_word][C], type [n_type][C], pos [n_pos][C] contiguous, Y [M][ldy].
+ *   AN ID OUTSIDE ITS TABLE IS CLAMPED INTO IT (below 0 -> row 0, at or above the size -> the last row): a kernel cannot report it
+ *   and must not read outside the table.  C % 8 == 0, 8 <= C <= 4096 (one wave holds a row); beyond that the call is refused.
+ * ---------------------------------------------------------------------- */
+int omg_gemm_skinny(int dtype, int M, int N, int K, const void* A, int64_t lda, const void* W, int64_t ldw, const void* bias,
+                    int gelu, const void* residual, int64_t ldr, void* C, int64_t ldc, void* stream);
+int omg_bert_embed_ln(int dtype, int M, int C, const int64_t* input_ids, const int64_t* token_type_ids, const int64_t* position_ids,
+                      const void* word, int n_word, const void* type, int n_type, const void* pos, int n_pos,
+                      const void* gamma, const void* beta, float eps, void* Y, int64_t ldy, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,8 @@ _DPT = ("DPTForDepthEstimation", "DPTImageProcessor", "DPTFeatureExtractor", "de
 _SWIN = ("SwinBackbone", "swin_from_groundingdino")
 _GDINO = ("GroundingDinoEncoder", "GroundingDinoEncoderOutput")
 _GDINO_DECODER = ("GroundingDinoDecoderHead", "GroundingDinoDetectionOutput", "GroundingDinoDetector")
-__all__ = list(_SAM) + list(_SAM_VIT) + list(_SEGMENT_ANYTHING) + list(_DPT) + list(_SWIN) + list(_GDINO) + list(_GDINO_DECODER)
+_BERT = ("BertTextEncoder",)
+__all__ = list(_SAM) + list(_SAM_VIT) + list(_SEGMENT_ANYTHING) + list(_DPT) + list(_SWIN) + list(_GDINO) + list(_GDINO_DECODER) + list(_BERT)
 
 
 def __getattr__(name):          # the segmenter's public names, imported on first use (omg_amd.sam pulls in torch and the kernels' bindings)
@@ -35,4 +36,7 @@ def __getattr__(name):          # the segmenter's public names, imported on firs
     if name in _GDINO_DECODER:
         from . import gdino_decoder
         return getattr(gdino_decoder, name)
+    if name in _BERT:
+        from . import bert
+        return getattr(bert, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -89,7 +89,9 @@ def text_masks_from_input_ids(input_ids: torch.Tensor, special_token_ids: Sequen
     special token."""
     B, T = input_ids.shape
     dev = input_ids.device
-    special = torch.isin(input_ids, torch.tensor(list(special_token_ids), device=dev))
+    special = torch.zeros_like(input_ids, dtype=torch.bool)
+    for s in special_token_ids:          # scalar compares, not torch.isin against a tensor made from the list: that is a host-to-device
+        special = special | (input_ids == int(s))    # copy, which a torch.cuda.graph capture of the detector's call does not permit
     idx = torch.arange(T, device=dev)[None].expand(B, -1)
     prev = torch.cummax(torch.where(special, idx, torch.full((), -1, device=dev)), dim=1)[0]
     nxt = torch.where(special, idx, torch.full((), T, device=dev))
@@ -405,22 +407,30 @@ def phrases(token_masks: torch.Tensor, input_ids: torch.Tensor, tokenizer, speci
 
 class GroundingDinoDetector(nn.Module):
     """``SwinBackbone`` -> a caller-supplied text module -> ``GroundingDinoEncoder`` -> ``GroundingDinoDecoderHead``.  The text module
-    is any callable ``(input_ids, attention_mask [B, T, T], token_type_ids, position_ids) -> last_hidden_state`` (the library's BERT
-    in torch)."""
+    is any callable ``(input_ids, attention_mask [B, T, T], token_type_ids, position_ids) -> last_hidden_state``: the library's BERT
+    in torch, or :class:`omg_amd.BertTextEncoder` on the HIP kernels (``from_pretrained(..., text_backbone="hip")``)."""
 
     def __init__(self, backbone, text_backbone, encoder, head):
         super().__init__()
         self.backbone, self.text_backbone, self.encoder, self.head = backbone, text_backbone, encoder, head
 
     @classmethod
-    def from_pretrained(cls, path, torch_dtype=torch.float16, device=None, **_ignored):
-        from transformers import AutoConfig, AutoModel
+    def from_pretrained(cls, path, torch_dtype=torch.float16, device=None, text_backbone: str = "torch", **_ignored):
+        """``text_backbone="torch"``: the library's BERT in torch, in fp32 (``torch_dtype`` does not apply to it); ``"hip"``:
+        :class:`omg_amd.BertTextEncoder` in ``torch_dtype`` — every network of the call then runs on the HIP kernels and the call is
+        capturable in one ``torch.cuda.graph``."""
         from .gdino import GroundingDinoEncoder
         from .swin import SwinBackbone
+        if text_backbone not in ("torch", "hip"):
+            raise L.OmgHipError(f"GroundingDinoDetector.from_pretrained: text_backbone='{text_backbone}'; 'torch' or 'hip'")
         config, sd = _read_checkpoint(path, "GroundingDinoDetector")
         backbone = SwinBackbone.from_pretrained(path, torch_dtype=torch_dtype, device=device, prefix="model.backbone.conv_encoder.model.")
         encoder = GroundingDinoEncoder.from_pretrained(path, torch_dtype=torch_dtype, device=device)
         head = GroundingDinoDecoderHead.from_pretrained(path, torch_dtype=torch_dtype, device=device)
+        if text_backbone == "hip":
+            from .bert import BertTextEncoder
+            return cls(backbone, BertTextEncoder.from_pretrained(path, torch_dtype=torch_dtype, device=device), encoder, head)
+        from transformers import AutoConfig, AutoModel
         tc = dict(config.get("text_config") or {})
         text = AutoModel.from_config(AutoConfig.for_model(tc.pop("model_type", "bert"), **tc), add_pooling_layer=False)
         pre = "model.text_backbone."

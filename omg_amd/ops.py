@@ -1182,6 +1182,56 @@ def gdino_ref_step(valid_ratios: torch.Tensor, *, ref_in: Optional[torch.Tensor]
     return ref_out, ref_input, emb
 
 
+def gemm_skinny(a: torch.Tensor, w: torch.Tensor, *, bias: Optional[torch.Tensor] = None, gelu: bool = False,
+                residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``out[M, N] = epi(a[M, K] @ w[N, K]^T)`` for few rows: bias, then the erf GELU, then the residual.  Rows may be column slices of
+    wider buffers (unit column stride).  omg_gemm_skinny."""
+    _dev(a)
+    M, K = a.shape
+    N = w.shape[0]
+    assert w.shape[1] == K and a.stride(1) == 1 and w.stride(1) == 1 and w.dtype == a.dtype
+    if out is None:
+        out = torch.empty((M, N), dtype=a.dtype, device=a.device)
+    assert out.shape == (M, N) and out.stride(1) == 1 and out.dtype == a.dtype
+    if residual is not None:
+        assert residual.shape == (M, N) and residual.stride(1) == 1 and residual.dtype == a.dtype
+    if bias is not None:
+        assert bias.shape == (N,) and bias.is_contiguous() and bias.dtype == a.dtype and bias.device == a.device
+    assert w.device == a.device and out.device == a.device and (residual is None or residual.device == a.device)
+    t0 = _PROF.begin() if _PROF is not None else None
+    L.check(L.lib().omg_gemm_skinny(_dt(a), M, N, K, a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), _p(bias), int(gelu),
+                                    _p(residual), residual.stride(0) if residual is not None else 0, out.data_ptr(), out.stride(0),
+                                    _stream()), "omg_gemm_skinny")
+    if _PROF is not None:
+        _PROF.end("gemm_skinny", 2.0 * M * N * K, t0, ("skinny", M, N, K))
+    return out
+
+
+def bert_embed_ln(input_ids: torch.Tensor, token_type_ids: torch.Tensor, position_ids: torch.Tensor, word: torch.Tensor,
+                  token_type: torch.Tensor, position: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``LayerNorm(word[input_ids] + token_type[token_type_ids] + position[position_ids])``: the ids int64 of one shape [...], the tables
+    [rows, C] contiguous -> [..., C].  An id outside its table is clamped into it.  omg_bert_embed_ln."""
+    _dev(word)
+    C_ = word.shape[1]
+    for t in (input_ids, token_type_ids, position_ids):
+        if t.dtype != torch.int64 or t.shape != input_ids.shape or not t.is_contiguous() or t.device != word.device:
+            raise L.OmgHipError("bert_embed_ln: the ids are contiguous int64 tensors of one shape on the tables' device")
+    for t in (word, token_type, position):
+        assert t.dim() == 2 and t.shape[1] == C_ and t.is_contiguous() and t.dtype == word.dtype and t.device == word.device
+    for t in (gamma, beta):
+        assert t.shape == (C_,) and t.is_contiguous() and t.dtype == word.dtype and t.device == word.device
+    M = input_ids.numel()
+    if out is None:
+        out = torch.empty(tuple(input_ids.shape) + (C_,), dtype=word.dtype, device=word.device)
+    assert out.is_contiguous() and out.numel() == M * C_ and out.dtype == word.dtype
+    L.check(L.lib().omg_bert_embed_ln(_dt(word), M, C_, input_ids.data_ptr(), token_type_ids.data_ptr(), position_ids.data_ptr(),
+                                      word.data_ptr(), word.shape[0], token_type.data_ptr(), token_type.shape[0], position.data_ptr(),
+                                      position.shape[0], gamma.data_ptr(), beta.data_ptr(), eps, out.data_ptr(), C_, _stream()),
+            "omg_bert_embed_ln")
+    return out
+
+
 def conv3x3_nhwc_ex(x: torch.Tensor, w: torch.Tensor, *, stride: int = 1, bias: Optional[torch.Tensor] = None, act: int = 0,
                     residual: Optional[torch.Tensor] = None, relu_in: bool = False, same: bool = False,
                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
