@@ -792,6 +792,31 @@ int omg_bert_embed_ln(int dtype, int M, int C, const int64_t* input_ids, const i
                       const void* word, int n_word, const void* type, int n_type, const void* pos, int n_pos,
                       const void* gamma, const void* beta, float eps, void* Y, int64_t ldy, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Pillow's 8-bit resize on the device, and what a preprocessor does behind it (omg_amd/image_prep.py).  Image.resize(size, resample) on
+ * an RGB image is two passes over tables that depend on the sizes alone (image_prep.resize_tables, float64 on the host, uploaded once):
+ *   bounds [out][2] int32: first input index and number of taps n of an output index; coeffs [out][ksize] int32: 22-bit fixed point.
+ *   a pass:  out = clip((2^21 + sum_{t < n} in[first + t] * coeff[t]) >> 22, 0, 255)  in 32-bit integers, per channel.
+ * The kernels read the tables and know no filter: BILINEAR and BICUBIC cost the same.  A window is clamped into its axis, so a table
+ * that is not resize_tables' own cannot make a kernel read outside the image.  No atomics, no workspace; the result is a function of
+ * the input and the tables alone, bit for bit what Pillow computes.
+ *
+ * omg_image_resize_h: the horizontal pass, uint8 in [B][H][W][3] -> uint8 out [B][H][OW][3], both contiguous; bounds / coeffs of W -> OW.
+ *   A wave stages the segment of its row that 64 outputs read in LDS through aligned dword loads (nothing behind the tensor is read:
+ *   its last partial dword goes byte by byte); a segment beyond 4 KiB or an input that is not 4-byte aligned is read from global memory.
+ * omg_image_resize_v: the vertical pass, uint8 in [B][H][W][3] -> OH rows; bounds / coeffs of H -> OH, or bounds NULL: OH == H, the
+ *   identity (the epilogue alone).  The epilogue:
+ *     lut NULL:  uint8 out [B][OH][W][3];
+ *     lut given: out [B][3][Hpad][Wpad] of out_dtype (OMG_F16 / OMG_BF16 / OMG_F32), out[b][c][y][x] = lut[c][value] with lut [3][256]
+ *                of out_dtype, and 0 for y >= OH or x >= W (Hpad >= OH, Wpad >= W): normalise, pad, permute and cast in the store.
+ * Refused with a message: NULL operands, sizes below 1, misaligned tables, a pad smaller than the image, an unknown out_dtype,
+ *   B H beyond 4 * 65535 rows (h), B beyond 65535 or more than 4 * 65535 output rows (v).
+ * ---------------------------------------------------------------------- */
+int omg_image_resize_h(int B, int H, int W, int OW, const uint8_t* in, const int32_t* bounds, const int32_t* coeffs, int ksize,
+                       uint8_t* out, void* stream);
+int omg_image_resize_v(int B, int H, int W, int OH, const uint8_t* in, const int32_t* bounds, const int32_t* coeffs, int ksize,
+                       int out_dtype, const void* lut, int Hpad, int Wpad, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -454,7 +454,8 @@ class _Batch(dict):
 
 class DPTImageProcessor:
     """``transformers.DPTImageProcessor`` for what a ``preprocessor_config.json`` carries: resize through PIL (``size``, ``resample``,
-    ``keep_aspect_ratio``, ``ensure_multiple_of``), rescale, normalise.  Host side, fp32 NCHW out; padding is not built."""
+    ``keep_aspect_ratio``, ``ensure_multiple_of``), rescale, normalise.  Host side, fp32 NCHW out; padding is not built.  Cuda uint8
+    [H, W, 3] tensors are prepared on the device instead (ops.image_prep), with the same bits, and ``pixel_values`` stays there."""
 
     def __init__(self, do_resize=True, size=None, resample=3, keep_aspect_ratio=False, ensure_multiple_of=1, do_rescale=True, rescale_factor=1 / 255,
                  do_normalize=True, image_mean=None, image_std=None, do_pad=False, **_ignored):
@@ -505,13 +506,32 @@ class DPTImageProcessor:
             a = (a - np.asarray(self.image_mean, dtype=np.float32)) / np.asarray(self.image_std, dtype=np.float32)
         return np.ascontiguousarray(a.transpose(2, 0, 1))
 
+    def _one_device(self, image: torch.Tensor) -> torch.Tensor:
+        """:meth:`_one` of a cuda uint8 [H, W, 3] tensor on the device -> fp32 [3, oh, ow]: Pillow's resize bit for bit and the numpy
+        lines above as a lookup table (ops.image_prep)."""
+        from . import image_prep
+        image = image.contiguous()
+        h, w = int(image.shape[0]), int(image.shape[1])
+        oh, ow = self.output_size(h, w) if self.do_resize else (h, w)
+        key = (image.device, self.do_rescale, self.rescale_factor, self.do_normalize, tuple(self.image_mean), tuple(self.image_std))
+        if getattr(self, "_lut_key", None) != key:
+            self._lut_key = key
+            self._lut_t = image_prep.lut_numpy_rescale_mean_std(self.rescale_factor if self.do_rescale else None,
+                                                                self.image_mean if self.do_normalize else None, self.image_std,
+                                                                torch.float32, image.device)
+        return ops.image_prep(image, (oh, ow), self.resample if self.do_resize else image_prep.BILINEAR, lut=self._lut_t)
+
     def __call__(self, images=None, return_tensors="pt", **_ignored):
+        """PIL images and numpy arrays go through the host; cuda uint8 [H, W, 3] tensors stay on the device and ``pixel_values`` is there."""
         if images is None:
             raise L.OmgHipError("DPTImageProcessor: images=...")
         if return_tensors != "pt":
             raise L.OmgHipError("DPTImageProcessor: return_tensors must be 'pt'")
         if not isinstance(images, (list, tuple)):
             images = [images]
+        on_device = [isinstance(im, torch.Tensor) and im.is_cuda and im.dtype == torch.uint8 and im.dim() == 3 and im.shape[2] == 3 for im in images]
+        if images and all(on_device):
+            return _Batch(pixel_values=torch.stack([self._one_device(im) for im in images]))
         return _Batch(pixel_values=torch.from_numpy(np.stack([self._one(im) for im in images])))
 
     preprocess = __call__

@@ -1583,3 +1583,73 @@ def geglu_row_perm(n_total: int) -> torch.Tensor:
     p = torch.arange(n_total)
     blk, j = p // 64, p % 64
     return torch.where(j < 32, blk * 32 + j, nh + blk * 32 + (j - 32))
+
+
+_LUT_DT = {torch.float16: L.OMG_F16, torch.bfloat16: L.OMG_BF16, torch.float32: L.OMG_F32}
+
+
+def image_prep(u8: torch.Tensor, out_hw: Tuple[int, int], resample: int, lut: Optional[torch.Tensor] = None,
+               pad_hw: Optional[Tuple[int, int]] = None, out_dtype: Optional[torch.dtype] = None,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``PIL.Image.resize((ow, oh), resample)`` of a contiguous cuda uint8 ``[H, W, 3]`` / ``[B, H, W, 3]`` image, bit for bit
+    (``resample`` 2 BILINEAR or 3 BICUBIC; omg_amd/image_prep.py has the arithmetic).  Without ``lut``: the resized uint8 image
+    ``[(B,) oh, ow, 3]``.  With ``lut`` ``[3, 256]`` of ``out_dtype`` (float16 / bfloat16 / float32): ``[(B,) 3, Hpad, Wpad]`` of that
+    dtype, ``out[c, y, x] = lut[c, resized[y, x, c]]`` and zeros in the pad at the right and bottom (``pad_hw``, default none).  Two
+    launches (omg_image_resize_h, omg_image_resize_v), one when an axis keeps its size; nothing else runs.  ``out``: the result's buffer."""
+    from . import image_prep as ip
+    if not isinstance(u8, torch.Tensor):
+        raise L.OmgHipError(f"image_prep takes a contiguous cuda uint8 [H, W, 3] or [B, H, W, 3] tensor, got {type(u8).__name__}")
+    if not u8.is_cuda or u8.dtype != torch.uint8 or u8.dim() not in (3, 4) or u8.shape[-1] != 3 or not u8.is_contiguous() or u8.numel() == 0:
+        raise L.OmgHipError(f"image_prep takes a contiguous cuda uint8 [H, W, 3] or [B, H, W, 3] tensor, got {u8.dtype} {tuple(u8.shape)} "
+                            f"on {u8.device}{'' if u8.is_contiguous() else ', not contiguous'}")
+    try:
+        resample = ip.check_resample(resample)
+    except ValueError as e:
+        raise L.OmgHipError(str(e)) from None
+    batched = u8.dim() == 4
+    B = u8.shape[0] if batched else 1
+    H, W = int(u8.shape[-3]), int(u8.shape[-2])
+    oh, ow = int(out_hw[0]), int(out_hw[1])
+    if oh < 1 or ow < 1:
+        raise L.OmgHipError(f"image_prep: out_hw {tuple(out_hw)}")
+    dev = u8.device
+    if lut is None:
+        if pad_hw is not None or out_dtype not in (None, torch.uint8):
+            raise L.OmgHipError("image_prep: pad_hw and out_dtype go with a lookup table (the planar output); without one the result is uint8 HWC")
+        code, hp, wp = 0, oh, ow
+        shape, dt_out = (B, oh, ow, 3), torch.uint8
+    else:
+        out_dtype = lut.dtype if out_dtype is None else out_dtype
+        if out_dtype not in _LUT_DT or lut.dtype != out_dtype or tuple(lut.shape) != (3, 256) or not lut.is_contiguous() or lut.device != dev:
+            raise L.OmgHipError(f"image_prep: the lookup table is a contiguous [3, 256] tensor of out_dtype (float16, bfloat16 or float32) on the "
+                                f"image's device, got {lut.dtype} {tuple(lut.shape)} on {lut.device} for out_dtype {out_dtype}")
+        hp, wp = (oh, ow) if pad_hw is None else (int(pad_hw[0]), int(pad_hw[1]))
+        if hp < oh or wp < ow:
+            raise L.OmgHipError(f"image_prep: pad_hw {(hp, wp)} is smaller than out_hw {(oh, ow)}")
+        code = _LUT_DT[out_dtype]
+        shape, dt_out = (B, 3, hp, wp), out_dtype
+    if out is None:
+        out = torch.empty(shape, dtype=dt_out, device=dev)
+    elif out.numel() != B * 3 * hp * wp or out.dtype != dt_out or not out.is_contiguous() or out.device != dev:
+        raise L.OmgHipError(f"image_prep: out is a contiguous {dt_out} tensor of {shape} on the image's device, got {out.dtype} {tuple(out.shape)}")
+    else:
+        out = out.view(shape)
+    lib = L.lib()
+    src = u8
+    if ow != W:
+        bx, cx = ip.device_tables(W, ow, resample, dev)
+        direct = oh == H and lut is None                       # the horizontal pass is the whole resize: straight into the result
+        mid = out if direct else torch.empty((B, H, ow, 3), dtype=torch.uint8, device=dev)
+        L.check(lib.omg_image_resize_h(B, H, W, ow, src.data_ptr(), bx.data_ptr(), cx.data_ptr(), cx.shape[1], mid.data_ptr(), _stream()),
+                "omg_image_resize_h")
+        if direct:
+            return out if batched else out[0]
+        src = mid
+    if oh != H:
+        by, cy = ip.device_tables(H, oh, resample, dev)
+        pb, pc, ks = by.data_ptr(), cy.data_ptr(), cy.shape[1]
+    else:
+        pb, pc, ks = None, None, 0
+    L.check(lib.omg_image_resize_v(B, H, ow, oh, src.data_ptr(), pb, pc, ks, code, _p(lut), hp, wp, out.data_ptr(), _stream()),
+            "omg_image_resize_v")
+    return out if batched else out[0]

@@ -117,7 +117,11 @@ class SamPromptEncoder(nn.Module):
 
     def _coords(self, pts: torch.Tensor) -> torch.Tensor:
         h, w = self.input_image_size
-        return self.pe_layer.encode((pts.float() + 0.5) / torch.tensor([w, h], dtype=torch.float32, device=pts.device))
+        key = ("wh", pts.device)                 # uploaded once: a captured call (GroundedSam.predict_masks) cannot upload it
+        wh = self._dense_pe.get(key)
+        if wh is None:
+            wh = self._dense_pe[key] = torch.tensor([w, h], dtype=torch.float32, device=pts.device)
+        return self.pe_layer.encode((pts.float() + 0.5) / wh)
 
     @torch.no_grad()
     def forward(self, points: Optional[Tuple[torch.Tensor, torch.Tensor]], boxes: Optional[torch.Tensor], masks: Optional[torch.Tensor] = None):
@@ -352,9 +356,38 @@ class EfficientViTSam(nn.Module):
         scale = long_side_length * 1.0 / max(oldh, oldw)
         return int(oldh * scale + 0.5), int(oldw * scale + 0.5)
 
-    def preprocess(self, image: np.ndarray) -> Tuple[np.ndarray, torch.Tensor]:
+    def _device_lut(self, dtype, device) -> torch.Tensor:
+        key = (dtype, torch.device(device))
+        if getattr(self, "_lut_key", None) != key:
+            from . import image_prep
+            self._lut_key = key
+            self._lut_t = image_prep.lut_unit_mean_std([v / 255 for v in self.pixel_mean], [v / 255 for v in self.pixel_std], dtype, device)
+        return self._lut_t
+
+    def preprocess_device(self, image: torch.Tensor, dtype: torch.dtype = torch.float32, want_image: bool = True):
+        """:meth:`preprocess` of a cuda uint8 [H, W, 3] image on the device (ops.image_prep: Pillow's bilinear resize bit for bit, the
+        normalisation as a lookup table of the host expression, pad and cast in the same launch) -> (the resized uint8 image or None,
+        the encoder's input [1, 3, S, S] in ``dtype``)."""
+        from . import image_prep
+        if not image.is_cuda or image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 3:
+            raise L.OmgHipError(f"EfficientViTSam.preprocess: a tensor image is a cuda uint8 [H, W, 3] tensor, got {image.dtype} "
+                                f"{tuple(image.shape)} on {image.device}")
+        image = image.contiguous()
+        side = self.image_size[1]
+        h, w = int(image.shape[0]), int(image.shape[1])
+        th, tw = (h, w) if max(h, w) == side else self.get_preprocess_shape(h, w, side)
+        x = ops.image_prep(image, (th, tw), image_prep.BILINEAR, lut=self._device_lut(dtype, image.device), pad_hw=(side, side))[None]
+        resized = None
+        if want_image:
+            resized = image if (th, tw) == (h, w) else ops.image_prep(image, (th, tw), image_prep.BILINEAR)
+        return resized, x
+
+    def preprocess(self, image):
         """HWC uint8 RGB -> (the resized uint8 image, the encoder's input [1, 3, S, S] fp32 on the host): the long side resized to
-        ``image_size[1]`` through PIL (bilinear, as torchvision resizes a PIL image), x / 255, mean / std, zero pad at the right and bottom."""
+        ``image_size[1]`` through PIL (bilinear, as torchvision resizes a PIL image), x / 255, mean / std, zero pad at the right and bottom.
+        A cuda uint8 tensor gives the same two, on the device (:meth:`preprocess_device`)."""
+        if isinstance(image, torch.Tensor):
+            return self.preprocess_device(image)
         from PIL import Image
         side = self.image_size[1]
         h, w, _ = image.shape
@@ -486,16 +519,26 @@ class EfficientViTSamPredictor:
         self.original_size = (int(hw[0]), int(hw[1]))
         self.input_size = self.model.get_preprocess_shape(*self.original_size, long_side_length=self.model.image_size[0])
 
-    def set_image(self, image: np.ndarray, image_format: str = "RGB") -> None:
+    def set_image(self, image, image_format: str = "RGB") -> None:
+        """``image``: HWC uint8, a numpy array (the host preprocessing) or a cuda tensor (the same bits from ops.image_prep's launches)."""
         assert image_format in ["RGB", "BGR"], f"image_format must be in ['RGB', 'BGR'], is {image_format}."
         if not self.device.type == "cuda":
             raise L.OmgHipError("EfficientViTSamPredictor needs its model on the MI355X (cuda/hip device); there is no CPU fallback")
+        dt = self.model.mask_decoder.iou_token.weight.dtype
+        if isinstance(image, torch.Tensor):
+            if image_format != self.model.image_format:
+                image = image.flip(-1)
+            _, x = self.model.preprocess_device(image, dtype=dt, want_image=False)
+            self.reset_image()
+            self._set_sizes(image.shape[:2])
+            self.features = self.model.image_encoder.forward_features(x)["out"]        # NHWC
+            self.is_image_set = True
+            return
         if image_format != self.model.image_format:
             image = image[..., ::-1]
         self.reset_image()
         self._set_sizes(image.shape[:2])
         _, x = self.model.preprocess(image)
-        dt = self.model.mask_decoder.iou_token.weight.dtype
         self.features = self.model.image_encoder.forward_features(x.to(self.device, dt))["out"]        # NHWC
         self.is_image_set = True
 

@@ -10,7 +10,8 @@
 
 ``Sam`` = the ViT image encoder (omg_amd/sam_vit.py) + ``SamPromptEncoder`` + ``SamMaskDecoder`` (omg_amd/sam.py, unchanged) under the
 checkpoint's own ``image_encoder.*`` / ``prompt_encoder.*`` / ``mask_decoder.*`` keys; ``postprocess_masks`` is omg_sam_postprocess.
-The resize of ``set_image`` goes through PIL on the uint8 image, as ``ResizeLongestSide.apply_image`` does.  A mask prompt is refused,
+The resize of ``set_image`` goes through PIL on the uint8 image, as ``ResizeLongestSide.apply_image`` does; a cuda uint8 image takes
+the same resize on the device (omg_amd/image_prep.py), fused with ``Sam.preprocess``.  A mask prompt is refused,
 as everywhere in omg_amd; ``SamAutomaticMaskGenerator`` is not built.
 """
 from __future__ import annotations
@@ -22,11 +23,17 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from . import ops
+from . import image_prep, ops
 from .sam import SamMaskDecoder, SamPromptEncoder
 from .sam_vit import SamImageEncoderViT
 
 __all__ = ["Sam", "SamPredictor", "ResizeLongestSide", "build_sam", "build_sam_vit_h", "build_sam_vit_l", "build_sam_vit_b", "sam_model_registry"]
+
+
+def _device_image(image: torch.Tensor, who: str) -> torch.Tensor:
+    if not image.is_cuda or image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 3:
+        raise L.OmgHipError(f"{who}: a tensor image is a cuda uint8 [H, W, 3] tensor, got {image.dtype} {tuple(image.shape)} on {image.device}")
+    return image.contiguous()
 
 
 class ResizeLongestSide:
@@ -40,10 +47,13 @@ class ResizeLongestSide:
         scale = long_side_length * 1.0 / max(oldh, oldw)
         return int(oldh * scale + 0.5), int(oldw * scale + 0.5)
 
-    def apply_image(self, image: np.ndarray) -> np.ndarray:
-        """HWC uint8 -> HWC uint8, bilinear through PIL (as torchvision resizes a PIL image)."""
-        from PIL import Image
+    def apply_image(self, image):
+        """HWC uint8 -> HWC uint8, bilinear through PIL (as torchvision resizes a PIL image).  A cuda uint8 tensor stays on the device:
+        the same resize, bit for bit, by ops.image_prep."""
         th, tw = self.get_preprocess_shape(image.shape[0], image.shape[1], self.target_length)
+        if isinstance(image, torch.Tensor):
+            return ops.image_prep(_device_image(image, "ResizeLongestSide.apply_image"), (th, tw), image_prep.BILINEAR)
+        from PIL import Image
         return np.array(Image.fromarray(np.ascontiguousarray(image)).resize((tw, th), Image.BILINEAR))
 
     def apply_coords(self, coords: np.ndarray, original_size: Tuple[int, ...]) -> np.ndarray:
@@ -124,10 +134,30 @@ class SamPredictor:
         self.original_size = None
         self.input_size = None
 
-    def set_image(self, image: np.ndarray, image_format: str = "RGB") -> None:
+    def _lut(self) -> torch.Tensor:
+        """Sam.preprocess as a [3, 256] table of the encoder's dtype (image_prep.lut_sam), built once."""
+        m = self.model
+        key = (m.dtype, m.device)
+        if getattr(self, "_lut_key", None) != key:
+            self._lut_key, self._lut_t = key, image_prep.lut_sam(m.pixel_mean, m.pixel_std, m.dtype)
+        return self._lut_t
+
+    def set_image(self, image, image_format: str = "RGB") -> None:
+        """``image``: HWC uint8, a numpy array (resized through PIL on the host, as the original) or a cuda tensor: then the resize,
+        Sam.preprocess, the pad and the cast are two launches of ops.image_prep on the device, with the same bits."""
         assert image_format in ["RGB", "BGR"], f"image_format must be in ['RGB', 'BGR'], is {image_format}."
         if self.device.type != "cuda":
             raise L.OmgHipError("SamPredictor needs its model on the MI355X (cuda/hip device); there is no CPU fallback")
+        if isinstance(image, torch.Tensor):
+            image = _device_image(image, "SamPredictor.set_image")
+            if image_format != self.model.image_format:
+                image = image.flip(-1).contiguous()
+            side = self.model.image_encoder.img_size
+            h, w = int(image.shape[0]), int(image.shape[1])
+            th, tw = self.transform.get_preprocess_shape(h, w, side)
+            x = ops.image_prep(image, (th, tw), image_prep.BILINEAR, lut=self._lut(), pad_hw=(side, side))[None]
+            self._set_encoder_input(x, (h, w), (th, tw))
+            return
         if image_format != self.model.image_format:
             image = image[..., ::-1]
         resized = self.transform.apply_image(image)
@@ -141,10 +171,14 @@ class SamPredictor:
                 ), f"set_torch_image input must be BCHW with long side {side}."
         if self.device.type != "cuda" or not transformed_image.is_cuda:
             raise L.OmgHipError("SamPredictor needs its model and image on the MI355X (cuda/hip device); there is no CPU fallback")
+        x = self.model.preprocess(transformed_image).to(self.model.dtype)
+        self._set_encoder_input(x, original_image_size, transformed_image.shape[-2:])
+
+    @torch.no_grad()
+    def _set_encoder_input(self, x: torch.Tensor, original_image_size, input_size) -> None:
         self.reset_image()
         self.original_size = (int(original_image_size[0]), int(original_image_size[1]))
-        self.input_size = tuple(int(v) for v in transformed_image.shape[-2:])
-        x = self.model.preprocess(transformed_image).to(self.model.dtype)
+        self.input_size = tuple(int(v) for v in input_size)
         self._features_nhwc = self.model.image_encoder.forward_features(x)["out"]
         self.features = self._features_nhwc.permute(0, 3, 1, 2)
         self.is_image_set = True
