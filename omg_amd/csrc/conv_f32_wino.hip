@@ -101,22 +101,35 @@ __global__ __launch_bounds__(256, 1) void conv_f32_wino_kernel(WinoP p) {
   const int offR = ((2 * (lane >> 3) + half) * 18 + 2 * (lane & 7)) * 32 + cq * 16;
   auto transform = [&](int buf, int rbuf) {
     const char* src = smem + 4 * WSTAGE + rbuf * WRAW + offR;
-    f32x4 ta[4], tb[4];
+    f32x4 d0[4], d1[4], d2[4], ta[4], v1[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      const f32x4 d0 = *(const f32x4*)(src + c * 32), d1 = *(const f32x4*)(src + (18 + c) * 32), d2 = *(const f32x4*)(src + (36 + c) * 32);
-      if (half == 0) { ta[c] = d0 - d2; tb[c] = d1 + d2; }      // rows d0 d1 d2: t0 = d0 - d2, t1 = d1 + d2
-      else           { ta[c] = d1 - d0; tb[c] = d0 - d2; }      // rows d1 d2 d3: t2 = d2 - d1, t3 = d1 - d3
+      d0[c] = *(const f32x4*)(src + c * 32); d1[c] = *(const f32x4*)(src + (18 + c) * 32); d2[c] = *(const f32x4*)(src + (36 + c) * 32);
+    }
+    // Differences before sums: on inputs with a common offset (post-SiLU activations) a difference of neighbours is exact and small, a
+    // sum is large and rounded.  Rows d0 d1 d2: t0 = d0 - d2 and t1 = d1 + d2 — the sum row takes its COLUMN transform first, per row,
+    // and adds last (rows first, t1's rounding, relative to 2 |d|, came out of the column differences relative to |V| << |d|).
+    // Rows d1 d2 d3 (d0 d1 d2 here): t2 = d2 - d1, t3 = d1 - d3, both differences.
+    if (half == 0) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) ta[c] = d0[c] - d2[c];
+      v1[0] = (d1[0] - d1[2]) + (d2[0] - d2[2]);
+      v1[1] = (d1[1] + d1[2]) + (d2[1] + d2[2]);
+      v1[2] = (d1[2] - d1[1]) + (d2[2] - d2[1]);
+      v1[3] = (d1[1] - d1[3]) + (d2[1] - d2[3]);
+    } else {
+      f32x4 tb[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) { ta[c] = d1[c] - d0[c]; tb[c] = d0[c] - d2[c]; }
+      v1[0] = tb[0] - tb[2]; v1[1] = tb[1] + tb[2]; v1[2] = tb[2] - tb[1]; v1[3] = tb[1] - tb[3];
     }
     char* dst = smem + buf * WSTAGE + (half * 8 * 2 + cq) * 1024 + lane * 16;
+    *(f32x4*)(dst + 0 * 2048) = ta[0] - ta[2];
+    *(f32x4*)(dst + 1 * 2048) = ta[1] + ta[2];
+    *(f32x4*)(dst + 2 * 2048) = ta[2] - ta[1];
+    *(f32x4*)(dst + 3 * 2048) = ta[1] - ta[3];
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const f32x4* tr = q ? tb : ta;
-      *(f32x4*)(dst + (q * 4 + 0) * 2048) = tr[0] - tr[2];
-      *(f32x4*)(dst + (q * 4 + 1) * 2048) = tr[1] + tr[2];
-      *(f32x4*)(dst + (q * 4 + 2) * 2048) = tr[2] - tr[1];
-      *(f32x4*)(dst + (q * 4 + 3) * 2048) = tr[1] - tr[3];
-    }
+    for (int j = 0; j < 4; ++j) *(f32x4*)(dst + (4 + j) * 2048) = v1[j];
   };
 
   const int wm = w >> 1, wn = w & 1;

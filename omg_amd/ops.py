@@ -409,12 +409,14 @@ def set_conv2d_f32_auto(winograd: bool = True, min_blocks: int = 256) -> None:
 
 
 def conv2d_f32(x: torch.Tensor, w: torch.Tensor, ksize: int, *, upsample: bool = False, bias: Optional[torch.Tensor] = None,
-               residual: Optional[torch.Tensor] = None, algo: str = "auto", wu: Optional[torch.Tensor] = None) -> torch.Tensor:
+               residual: Optional[torch.Tensor] = None, algo: str = "auto", wu: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """fp32 NHWC convolution on the f32-input MFMA: the up blocks of the upcast VAE decode.
     ``w``: fp32 [Cout, ksize*ksize*Cin] (pack_conv_weight of the fp32 OIHW tensor).  ``wu``: the Winograd image of the same weight
     (pack_conv_weight_wino).  ``algo``: "direct" = omg_conv2d_f32 (exact direct convolution), "winograd" = omg_conv2d_f32_wino
     (F(2x2, 3x3); needs ``wu``, ksize 3, even output sizes, Cin % 8 == 0 — an error otherwise), "auto" = Winograd where it applies and
-    the launch fills the machine (at least one 16 x 16 x 64 block per CU), else direct."""
+    the launch fills the machine (at least one 16 x 16 x 64 block per CU), else direct.  ``out``: a contiguous fp32 tensor of the
+    output's shape to write into (must not alias ``x``)."""
     global LAST_CONV2D_F32_ALGO
     _dev(x)
     assert x.dtype == torch.float32 and w.dtype == torch.float32 and x.is_contiguous() and w.is_contiguous()
@@ -428,7 +430,11 @@ def conv2d_f32(x: torch.Tensor, w: torch.Tensor, ksize: int, *, upsample: bool =
         raise L.OmgHipError("conv2d_f32(algo='winograd') needs ksize 3, even output sizes, Cin % 8 == 0 and the wu weight image")
     use_wino = algo == "winograd" or (algo == "auto" and wino_ok and _F32_AUTO["winograd"]
                                       and B * ((Ho + 15) // 16) * ((Wo + 15) // 16) * ((Cout + 63) // 64) >= _F32_AUTO["min_blocks"])
-    y = torch.empty((B, Ho, Wo, Cout), dtype=torch.float32, device=x.device)
+    if out is None:
+        y = torch.empty((B, Ho, Wo, Cout), dtype=torch.float32, device=x.device)
+    else:
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (B, Ho, Wo, Cout) and out.device == x.device
+        y = out
     if bias is not None:
         assert bias.dtype == torch.float32
     if residual is not None:
@@ -1553,10 +1559,13 @@ def pack_conv_weight_wino(w_oihw: torch.Tensor) -> torch.Tensor:
     [ceil(Cout / 64)][Cin / 8][pos 16][k chunk 2][row 64][4], zero rows beyond Cout.  Built once per weight."""
     co, ci, kh, kw = w_oihw.shape
     assert kh == 3 and kw == 3 and ci % 8 == 0 and w_oihw.dtype == torch.float32
-    def g_rows(t, dim):                                            # G t along ``dim``: [t0, (t0 + t1 + t2) / 2, (t0 - t1 + t2) / 2, t2], elementwise fp32
+    def g_rows(t, dim):                                            # G t along ``dim``: [t0, (t0 + t1 + t2) / 2, (t0 - t1 + t2) / 2, t2]
         t0, t1, t2 = t.unbind(dim)
         return torch.stack((t0, (t0 + t1 + t2) * 0.5, (t0 - t1 + t2) * 0.5, t2), dim)
-    u = g_rows(g_rows(w_oihw, 2), 3)                                # [Cout, Cin, 4, 4]
+    # in float64, rounded to fp32 once: a sum of up to nine fp32 taps is exact to 2^-53 there, so every U is within half an ulp of its own
+    # value.  Formed in fp32, a U whose taps cancel (a zero-sum filter's middle positions) carried an error relative to the taps instead,
+    # which the large V of the same positions (sums of four pixels) multiplied up
+    u = g_rows(g_rows(w_oihw.double(), 2), 3).float()              # [Cout, Cin, 4, 4]
     nb = (co + 63) // 64
     up = torch.zeros((nb * 64, ci, 4, 4), dtype=torch.float32, device=w_oihw.device)
     up[:co] = u
