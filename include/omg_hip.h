@@ -817,6 +817,51 @@ int omg_image_resize_h(int B, int H, int W, int OW, const uint8_t* in, const int
 int omg_image_resize_v(int B, int H, int W, int OH, const uint8_t* in, const int32_t* bounds, const int32_t* coeffs, int ksize,
                        int out_dtype, const void* lut, int Hpad, int Wpad, void* out, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Building one weight slot of a LoRA bank (omg_amd/lora.py, LoraBank.build): the merge of up to OMG_LORA_MAX_TERMS adapter terms into the
+ * 16-bit base weight W [N][K] (a Linear's [out][in], a convolution's packed [out][tap * Cin + cin]), all arithmetic in fp32:
+ *
+ *     out[n][k] = round16( W[n][k] * (1 + sum_t (gain_t[n] - 1)) + sum_t gain_t[n] * s_t * D_t[n][k] )        gain_t == 1 where NULL
+ *
+ * A term's dense delta D_t never goes to memory; it is formed per 32 x 64 tile in registers from the term's small fp32 factors (the sum
+ * of the terms crosses LDS once, to meet W in row-major order):
+ *   OMG_LORA_PLAIN  D = f0 [N][r] . f1 [r][K]                                       (lora_up . lora_down)
+ *   OMG_LORA_HADA   D = (f0 [N][r] . f1 [r][K]) * (f2 [N][r2] . f3 [r2][K])          elementwise (LoHa)
+ *   OMG_LORA_KRON   D[ia * c + ic][tap * (b * d) + ib * d + id] = f0[ia][ib] * f1[ic][tap][id]     f0 [a][b], f1 [c][taps][d] (LoKr)
+ *                   with a * c == N and taps * b * d == K.
+ * The products of PLAIN and HADA run on v_mfma_f32_32x32x2_f32: exact fp32 products, one fmaf chain per element over the rank in one
+ * fixed order (ranks are padded to a multiple of eight with zero products).  An element's value depends on its own row and column only — not
+ * on N, on its tile or on the other rows.  W is read once, out written once, one rounding at the store; out may be W itself.
+ *
+ * omg_lora_rownorm: norm[n] = sqrt(sum_k (W[n][k] + s * D[n][k])^2) of ONE term (DoRA's weight norm; the term's gain is ignored).  A
+ *   workgroup owns 32 rows: four waves take the 64-column tiles round robin, a lane adds its squares in ascending column order, the
+ *   partial sums are folded in a fixed order.  No atomics, no workspace: the result is a function of the operands alone.
+ * Refused with a message: dtype, NULL operands, N < 1, K < 8 or K % 8 != 0, more than OMG_LORA_MAX_TERMS terms, an unknown kind,
+ *   r < 1, a KRON whose dims do not multiply to N and K, a misaligned W / out.
+ * ---------------------------------------------------------------------- */
+enum { OMG_LORA_PLAIN = 0, OMG_LORA_HADA = 1, OMG_LORA_KRON = 2 };
+#define OMG_LORA_MAX_TERMS 4
+typedef struct {
+  int32_t kind;            /* OMG_LORA_PLAIN / HADA / KRON */
+  int32_t r, r2;           /* PLAIN: r; HADA: ranks of the first and the second product; KRON: unused */
+  int32_t a, b, c, d, taps; /* KRON only */
+  float s;                 /* the whole scaling of the term */
+  int32_t pad_;
+  const float* f0;
+  const float* f1;
+  const float* f2;
+  const float* f3;
+  const float* gain;       /* [N] or NULL */
+} omg_lora_term;
+typedef struct {
+  int32_t dtype, N, K, n_terms;
+  const void* W;           /* [N][K] of dtype */
+  void* out;               /* [N][K] of dtype: one slot of the stack */
+  omg_lora_term terms[OMG_LORA_MAX_TERMS];
+} omg_lora_merge_args;
+int omg_lora_rownorm(int dtype, int N, int K, const void* W, const omg_lora_term* term, float* norm, void* stream);
+int omg_lora_merge(const omg_lora_merge_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

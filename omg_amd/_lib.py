@@ -137,6 +137,26 @@ class StepArgs(C.Structure):
     ]
 
 
+LORA_PLAIN, LORA_HADA, LORA_KRON = 0, 1, 2
+LORA_MAX_TERMS = 4
+
+
+class LoraTermDesc(C.Structure):
+    _fields_ = [
+        ("kind", c_i32), ("r", c_i32), ("r2", c_i32),
+        ("a", c_i32), ("b", c_i32), ("c", c_i32), ("d", c_i32), ("taps", c_i32),
+        ("s", c_f32), ("pad_", c_i32),
+        ("f0", c_vp), ("f1", c_vp), ("f2", c_vp), ("f3", c_vp), ("gain", c_vp),
+    ]
+
+
+class LoraMergeArgs(C.Structure):
+    _fields_ = [
+        ("dtype", c_i32), ("N", c_i32), ("K", c_i32), ("n_terms", c_i32),
+        ("W", c_vp), ("out", c_vp), ("terms", LoraTermDesc * LORA_MAX_TERMS),
+    ]
+
+
 # every symbol include/omg_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "omg_abi_version": (c_i32, []),
@@ -218,6 +238,8 @@ SYMBOLS = {
     "omg_bert_embed_ln": (c_i32, [c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_f32, c_vp, c_i64, c_vp]),
     "omg_image_resize_h": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "omg_image_resize_v": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp]),
+    "omg_lora_rownorm": (c_i32, [c_i32, c_i32, c_i32, c_vp, C.POINTER(LoraTermDesc), c_vp, c_vp]),
+    "omg_lora_merge": (c_i32, [C.POINTER(LoraMergeArgs), c_vp]),
     "omg_debug_set_glds": (None, [c_i32]),
     "omg_debug_set_gemm_variant": (None, [c_i32]),
     "omg_debug_choose_variant": (c_i32, [c_i32, c_i32, c_i32, c_i32]),

@@ -16,7 +16,18 @@ styles for the UNet part of a LoRA file:
 
 Convolution entries (kohya ``conv_dim``, LyCORIS "LoCon", PEFT ``target_modules`` naming ``conv1`` / ``conv2`` ...) come in the same
 three key styles with a 4-D down weight ``[r, Cin, k, k]`` and an up weight ``[Cout, r, 1, 1]``; ``load_lora_adapter`` accepts them
-for the convolutions of :func:`conv_module_paths`.  LoHa / LoKr / Tucker / DoRA files are refused by name.
+for the convolutions of :func:`conv_module_paths`.
+
+LyCORIS LoHa (``hada_w1_a [out, r]``, ``hada_w1_b [r, in k k]``, ``hada_w2_a``, ``hada_w2_b``; delta = (w1_a . w1_b) * (w2_a . w2_b)) and LoKr
+(``lokr_w1 [a, b]`` or ``lokr_w1_a`` . ``lokr_w1_b``; ``lokr_w2 [c, d(, k, k)]`` or ``lokr_w2_a`` . ``lokr_w2_b``; delta = kron(w1, w2)) are
+recognised in the kohya / LyCORIS namespace (diffusers and SGM module names), on the same Linear and convolution targets and on the text
+encoders; a DoRA magnitude (``dora_scale [out, 1]`` / ``[out, 1, 1, 1]`` / ``[out]``, or PEFT's ``lora_magnitude_vector [out]`` with an optional
+``.weight`` / adapter-name segment) on any of them or on a plain pair.  Such modules become :class:`omg_amd.lora.LoraTerm` entries of
+``adapter.terms`` with the factor ``alpha / r`` (1 without ``alpha``; 1 for a LoKr of two full matrices whatever ``alpha`` holds) kept beside
+the fp32 factors; a file of plain pairs only gives the adapter it always gave.  Refused by name, every message carrying the words
+``LoHa / LoKr / Tucker``: Tucker forms (``lora_mid``, ``hada_t1``, ``hada_t2``, ``lokr_t2``), a ``dora_scale`` of shape ``[1, in]`` (LyCORIS's
+over-input form, which PEFT does not have), two algebras on one module, an incomplete or mis-shaped factor set, a magnitude on a
+text-encoder module.  The LoHa / LoKr rules follow LyCORIS's published behaviour and the DoRA rule PEFT's; neither package is pinned here.
 
 All are mapped onto the module paths of :class:`omg_amd.unet.UNet2DConditionModel` (whose state-dict keys equal
 diffusers', boundary B4) and returned as a :class:`omg_amd.lora.LoraAdapter`.  A per-layer ``alpha`` (kohya) is folded
@@ -35,7 +46,7 @@ from typing import Dict, Iterable, List, Optional, Tuple
 
 import torch
 
-from .lora import LoraAdapter
+from .lora import LoraAdapter, LoraTerm
 from .modules import Linear, lora_conv_targets
 
 
@@ -140,6 +151,73 @@ _CONV_BOUNDARY = ("conv_in", "conv_out")
 _CONV_BOUNDARY_FLAT = ("conv_in", "conv_out", "input_blocks_0_0", "out_2")          # the same two layers in kohya's flat / SGM names
 # other adapter algebras that share the lora_unet_* / PEFT namespaces (LyCORIS LoHa, LoKr, Tucker-decomposed LoCon, DoRA)
 _FOREIGN = ("hada_", "lokr_", "lora_mid", "dora_scale", "lora_magnitude_vector")
+_LYCO_WHAT = r"(?P<what>hada_w[12]_[ab]|hada_t[12]|lokr_w[12](?:_[ab])?|lokr_t2|lora_mid(?:\.weight)?|dora_scale)"
+_LYCO = re.compile(r"^lora_unet_(?P<flat>.+)\." + _LYCO_WHAT + "$")
+_LYCO_TE = re.compile(r"^lora_te(?P<n>[12]?)_(?P<flat>.+)\." + _LYCO_WHAT + "$")
+_PEFT_MAG = re.compile(r"^(?P<mod>.+)\.lora_magnitude_vector(?:\.[^.]+){0,2}$")        # bare, .weight, .<adapter>, .<adapter>.weight
+_TUCKER = ("lora_mid", "lora_mid.weight", "hada_t1", "hada_t2", "lokr_t2")
+_HADA = ("hada_w1_a", "hada_w1_b", "hada_w2_a", "hada_w2_b")
+
+
+def _family_error(key: str, reason: str) -> "LoaderError":
+    return LoaderError(f"LoHa / LoKr / Tucker (lora_mid) / DoRA entry {key!r}: {reason}")
+
+
+def _magnitude(key: str, t: torch.Tensor, n_out: Optional[int]) -> torch.Tensor:
+    """DoRA's per-output-channel magnitude as fp32 ``[out]``: ``[out, 1]``, ``[out, 1, 1, 1]`` or ``[out]`` in the file.  LyCORIS's
+    over-input form ``[1, in]`` has no PEFT counterpart and is refused by name."""
+    shape = tuple(t.shape)
+    if len(shape) == 2 and shape[0] == 1 and shape[1] > 1:
+        raise _family_error(key, f"a magnitude of shape {shape} runs over the input axis (LyCORIS wd_on_out=False); only per-output-channel "
+                                 f"magnitudes are supported")
+    if not (len(shape) in (1, 2, 4) and all(d == 1 for d in shape[1:])) or (n_out is not None and shape[0] != n_out):
+        raise _family_error(key, f"a magnitude of shape {shape} is not [out, 1], [out, 1, 1, 1] or [out]"
+                                 + (f" with out = {n_out}" if n_out is not None else ""))
+    return t.float().reshape(-1)
+
+
+def _make_term(key: str, f: Dict[str, torch.Tensor], alpha: Optional[float], conv: Optional[Tuple[int, int, int]]) -> LoraTerm:
+    """The LoHa / LoKr term of one module from its file entries ``f`` (suffix -> tensor, the magnitude excluded); ``conv`` =
+    ``(Cin, Cout, k)`` of a convolution target, ``None`` for a Linear, whose own shape is checked when the bank is built."""
+    names = set(f)
+    hada, kron = sorted(n for n in names if n.startswith("hada_")), sorted(n for n in names if n.startswith("lokr_"))
+    if hada and kron:
+        raise _family_error(key, "LoHa and LoKr factors on one module; one algebra per module and file")
+    taps = conv[2] * conv[2] if conv else 1
+    if hada:
+        if tuple(hada) != _HADA:
+            raise _family_error(key, f"incomplete LoHa factor set: has {hada}, needs {list(_HADA)}")
+        a1, b1, a2, b2 = (f[n] for n in _HADA)
+        ok = all(t.dim() == 2 for t in (a1, b1, a2, b2)) and a1.shape[1] == b1.shape[0] and a2.shape[1] == b2.shape[0] \
+            and a1.shape[0] == a2.shape[0] and b1.shape[1] == b2.shape[1] and min(a1.shape[1], a2.shape[1]) >= 1
+        if ok and conv:
+            ok = a1.shape[0] == conv[1] and b1.shape[1] == conv[0] * taps
+        if not ok:
+            raise _family_error(key, "LoHa factor shapes " + ", ".join(f"{n} {tuple(f[n].shape)}" for n in _HADA) + " are not [out, r], [r, in k k] twice"
+                                     + (f" for a {conv[2]}x{conv[2]} convolution {conv[0]} -> {conv[1]}" if conv else ""))
+        return LoraTerm("hada", {n: f[n] for n in _HADA}, alpha)
+    ops_ = {}
+    for w in ("lokr_w1", "lokr_w2"):
+        full, fa, fb = w in names, w + "_a" in names, w + "_b" in names
+        if full == (fa or fb) or fa != fb:
+            raise _family_error(key, f"incomplete LoKr factor set: {w} needs either {w} or both {w}_a and {w}_b, has {kron}")
+        ops_[w] = (f[w],) if full else (f[w + "_a"], f[w + "_b"])
+    def shape_of(op):                                    # (rows, columns) of the operand, a 4-D w2 flattened to [c, d k k]
+        if len(op) == 1:
+            return op[0].shape[0], op[0][0].numel()
+        return op[0].shape[0], op[1].shape[1]
+    ok = all(t.dim() == 2 for op in ops_.values() for t in op if len(op) == 2) and ops_["lokr_w1"][0].dim() == 2 \
+        and ops_["lokr_w2"][0].dim() in ((2, 4) if len(ops_["lokr_w2"]) == 1 else (2,)) \
+        and all(op[0].shape[1] == op[1].shape[0] and op[0].shape[1] >= 1 for op in ops_.values() if len(op) == 2)
+    if ok and conv:
+        (a, b), (c, dk) = shape_of(ops_["lokr_w1"]), shape_of(ops_["lokr_w2"])
+        w2 = ops_["lokr_w2"][0]
+        ok = a * c == conv[1] and dk % taps == 0 and b * (dk // taps) == conv[0] and (len(ops_["lokr_w2"]) == 2 or taps == 1 or
+                                                                                      (w2.dim() == 4 and tuple(w2.shape[2:]) == (conv[2], conv[2])))
+    if not ok:
+        raise _family_error(key, "LoKr factor shapes " + ", ".join(f"{n} {tuple(f[n].shape)}" for n in kron) + " do not give w1 [a, b] and w2 [c, d(, k, k)]"
+                                 + (f" with a c = {conv[1]}, b d = {conv[0]}, k = {conv[2]}" if conv else ""))
+    return LoraTerm("kron", {n: f[n] for n in kron}, alpha)
 
 
 def conv_module_paths(unet: torch.nn.Module) -> Dict[str, Tuple[int, int, int]]:
@@ -165,24 +243,22 @@ def parse_lora_state_dict(sd: Dict[str, torch.Tensor], module_paths: Iterable[st
     """Key-style detection + mapping (see the module docstring).  Returns ``(adapter, skipped_keys)``; raises
     ``LoaderError`` for a UNet entry that names no Linear layer of ``module_paths`` and no convolution of ``conv_paths``
     (``{path: (Cin, Cout, k)}``, :func:`conv_module_paths`; ``None``: Linear targets only) or for a half-present pair.  With
-    ``conv_paths`` it also raises, by name, for a down kernel that is not the base layer's, an up weight that is not 1x1, an entry
-    for ``conv_in`` / ``conv_out`` and for LoHa / LoKr / Tucker / DoRA keys.  ``skipped_keys`` lists what was neither UNet nor
+    ``conv_paths`` it also raises, by name, for a down kernel that is not the base layer's, an up weight that is not 1x1 and an entry
+    for ``conv_in`` / ``conv_out``.  LoHa / LoKr factors and DoRA magnitudes go to ``adapter.terms`` (module docstring); what is refused of
+    them is refused by name.  ``skipped_keys`` lists what was neither UNet nor
     text-encoder material."""
     paths = set(module_paths)
     convs = dict(conv_paths or {})
     flat = {p.replace(".", "_"): p for p in list(paths) + list(convs)}
-    if conv_paths is not None:
-        foreign = sorted(k for k in sd if any(f in k for f in _FOREIGN))
-        if foreign:
-            raise LoaderError(f"{foreign[0]!r}: LoHa / LoKr / Tucker (lora_mid) / DoRA entries are not plain LoRA pairs and are not "
-                              f"supported ({len(foreign)} such keys)")
     # key = ("unet", module) or ("te", 1 | 2, module)
     down: Dict[tuple, torch.Tensor] = {}
     up: Dict[tuple, torch.Tensor] = {}
     alpha: Dict[tuple, float] = {}
+    extra: Dict[tuple, Dict[str, torch.Tensor]] = {}       # LoHa / LoKr factors, Tucker cores and magnitudes per module, under their file suffix
+    extra_key: Dict[tuple, str] = {}                       # the first such file key of a module, for messages
     skipped: List[str] = []
 
-    def put(mod: str, which: str, t: torch.Tensor, key: str):
+    def resolve(mod: str, key: str) -> str:
         if mod.endswith(".to_out") and mod + ".0" in paths:      # diffusers' Attention.to_out is [Linear, Dropout]
             mod = mod + ".0"
         if conv_paths is not None and mod in _CONV_BOUNDARY:
@@ -190,12 +266,50 @@ def parse_lora_state_dict(sd: Dict[str, torch.Tensor], module_paths: Iterable[st
         if mod not in paths and mod not in convs:
             raise LoaderError(f"LoRA entry {key!r} targets {mod!r}, which is not a Linear layer of this UNet "
                               + ("(LoRA on conv layers is not supported)" if conv_paths is None else "nor one of its LoRA-capable convolutions"))
-        (down if which == "down" else up)[("unet", mod)] = t
+        return mod
+
+    def put(mod: str, which: str, t: torch.Tensor, key: str):
+        (down if which == "down" else up)[("unet", resolve(mod, key))] = t
+
+    def kohya_module(flat_name: str, key: str) -> str:
+        mod = flat.get(flat_name) or flat.get(sgm_flat_to_diffusers_flat(flat_name, layers_per_block))
+        if mod is None and conv_paths is not None and flat_name in _CONV_BOUNDARY_FLAT:
+            raise LoaderError(f"kohya LoRA entry {key!r} targets conv_in / conv_out, which are not LoRA targets")
+        if mod is None:
+            raise LoaderError(f"kohya LoRA entry {key!r} matches no Linear layer of this UNet "
+                              f"(LoRA on conv layers is not supported)")
+        return mod
+
+    def put_extra(k: tuple, what: str, t: torch.Tensor, key: str):
+        extra.setdefault(k, {})[what] = t
+        extra_key.setdefault(k, key)
+
+    def foreign(key: str, t: torch.Tensor):
+        """A key of another algebra (LoHa, LoKr, Tucker) or a DoRA magnitude: kohya / LyCORIS names, or PEFT's magnitude vector."""
+        m = _LYCO_TE.match(key)
+        if m:
+            put_extra(("te", 2 if m["n"] == "2" else 1, _te_unflatten(m["flat"])), m["what"], t, key)
+            return
+        m = _LYCO.match(key)
+        if m:
+            put_extra(("unet", kohya_module(m["flat"], key)), m["what"], t, key)
+            return
+        m = _PEFT_MAG.match(key)
+        if m:
+            if _TE_MOD.match(key):
+                raise _family_error(key, "a DoRA magnitude on a text-encoder module is not supported")
+            mod = m["mod"][5:] if m["mod"].startswith("unet.") else m["mod"]
+            put_extra(("unet", resolve(mod, key)), "dora_scale", t, key)
+            return
+        raise _family_error(key, "not a key of the kohya / LyCORIS namespace (lora_unet_<module>.<factor>) nor PEFT's lora_magnitude_vector")
 
     def put_te(n: int, mod: str, which: str, t: torch.Tensor):
         (down if which == "down" else up)[("te", n, mod)] = t
 
     for key, t in sd.items():
+        if any(f in key for f in _FOREIGN):
+            foreign(key, t)
+            continue
         m = _KOHYA_TE.match(key)
         if m:
             k = ("te", 2 if m["n"] == "2" else 1, _te_unflatten(m["flat"]))
@@ -228,12 +342,7 @@ def parse_lora_state_dict(sd: Dict[str, torch.Tensor], module_paths: Iterable[st
             continue
         m = _KOHYA.match(key)
         if m:
-            mod = flat.get(m["flat"]) or flat.get(sgm_flat_to_diffusers_flat(m["flat"], layers_per_block))
-            if mod is None and conv_paths is not None and m["flat"] in _CONV_BOUNDARY_FLAT:
-                raise LoaderError(f"kohya LoRA entry {key!r} targets conv_in / conv_out, which are not LoRA targets")
-            if mod is None:
-                raise LoaderError(f"kohya LoRA entry {key!r} matches no Linear layer of this UNet "
-                                  f"(LoRA on conv layers is not supported)")
+            mod = kohya_module(m["flat"], key)
             if m["what"] == "alpha":
                 alpha[("unet", mod)] = float(t)
             else:
@@ -241,7 +350,32 @@ def parse_lora_state_dict(sd: Dict[str, torch.Tensor], module_paths: Iterable[st
             continue
         skipped.append(key)
 
-    if not any(k[0] == "unet" for k in list(down) + list(up)):
+    # ---- the other algebras and the magnitudes: one LoraTerm per module, refusals by name
+    terms: Dict[str, LoraTerm] = {}
+    te_terms: Dict[tuple, LoraTerm] = {}
+    for k in sorted(extra, key=str):
+        f, key = dict(extra[k]), extra_key[k]
+        tucker = sorted(n for n in f if n in _TUCKER)
+        if tucker:
+            raise _family_error(key, f"Tucker-decomposed factors ({', '.join(tucker)}) are not supported")
+        mag = f.pop("dora_scale", None)
+        has_pair = k in down or k in up
+        if f and has_pair:
+            raise _family_error(key, "a plain lora_down / lora_up pair and LoHa / LoKr factors on one module; one algebra per module and file")
+        if mag is not None and k[0] == "te":
+            raise _family_error(key, "a DoRA magnitude on a text-encoder module is not supported")
+        if not f and not has_pair:
+            raise _family_error(key, "incomplete factor set: a magnitude without the factors of its delta")
+        if not f:
+            continue                                           # a magnitude on a plain pair: attached where the pairs are formed, below
+        term = _make_term(key, f, alpha.get(k), convs.get(k[1]) if k[0] == "unet" else None)
+        if mag is not None:
+            term.magnitude = _magnitude(key, mag, term.out_features)
+        if k[0] == "unet":
+            terms[k[1]] = term
+        else:
+            te_terms[k] = term
+    if not any(k[0] == "unet" for k in list(down) + list(up)) and not terms:
         raise LoaderError("no UNet LoRA entries found (expected PEFT lora_A/lora_B, diffusers lora.down/up or kohya lora_unet_* keys)")
     half = sorted(str(k) for k in set(down) ^ set(up))
     if half:
@@ -260,19 +394,27 @@ def parse_lora_state_dict(sd: Dict[str, torch.Tensor], module_paths: Iterable[st
             if b.dim() not in (2, 4) or tuple(b.shape[:2]) != (cout, a.shape[0]):
                 raise LoaderError(f"LoRA shapes of {k}: down {tuple(a.shape)}, up {tuple(b.shape)}")
             b = b.reshape(cout, a.shape[0])
+            if k in extra:                                       # a DoRA magnitude: the pair stays a term, alpha / r unfolded
+                terms[k[1]] = LoraTerm("plain", {"lora_down": a, "lora_up": b}, alpha.get(k), _magnitude(extra_key[k], extra[k]["dora_scale"], cout))
+                continue
             if k in alpha:
                 b = b * (alpha[k] / a.shape[0])
             weights[k[1]] = (a, b)
             continue
         if a.dim() != 2 or b.dim() != 2 or b.shape[1] != a.shape[0]:
             raise LoaderError(f"LoRA shapes of {k}: down {tuple(a.shape)}, up {tuple(b.shape)}")
+        if k in extra:
+            terms[k[1]] = LoraTerm("plain", {"lora_down": a, "lora_up": b}, alpha.get(k), _magnitude(extra_key[k], extra[k]["dora_scale"], b.shape[0]))
+            continue
         if k in alpha:
             b = b * (alpha[k] / a.shape[0])
         if k[0] == "unet":
             weights[k[1]] = (a, b)
         else:
             te.setdefault(k[1], {})[k[2]] = (a, b)
-    return LoraAdapter(name, weights, alpha=None, text_encoder=te), skipped
+    for k, term in te_terms.items():
+        te.setdefault(k[1], {})[k[2]] = term
+    return LoraAdapter(name, weights, alpha=None, text_encoder=te, terms=terms), skipped
 
 
 def load_lora_adapter(unet: torch.nn.Module, path_or_dict, adapter_name: Optional[str] = None) -> LoraAdapter:
@@ -298,8 +440,11 @@ def lora_state_dict(adapter: LoraAdapter, style: str = "peft") -> Dict[str, torc
     out: Dict[str, torch.Tensor] = {}
     for n, mods in adapter.text_encoder.items():
         pre = "text_encoder" if n == 1 else "text_encoder_2"
-        for mod, (a, b) in mods.items():
-            a, b = a.contiguous(), b.contiguous()
+        for mod, pair in mods.items():
+            if isinstance(pair, LoraTerm):
+                _write_term(out, f"lora_te{n}_" + mod.replace(".", "_"), pair, style)
+                continue
+            a, b = pair[0].contiguous(), pair[1].contiguous()
             if style == "peft":
                 out[f"{pre}.{mod}.lora_A.weight"], out[f"{pre}.{mod}.lora_B.weight"] = a, b
             elif style == "diffusers":
@@ -322,4 +467,22 @@ def lora_state_dict(adapter: LoraAdapter, style: str = "peft") -> Dict[str, torc
             out[f"{flat}.alpha"] = torch.tensor(float(adapter.alpha if adapter._alpha_given else a.shape[0]))
         else:
             raise ValueError(style)
+    for mod, term in adapter.terms.items():
+        _write_term(out, "lora_unet_" + mod.replace(".", "_"), term, style)
     return out
+
+
+def _write_term(out: Dict[str, torch.Tensor], flat: str, term: LoraTerm, style: str) -> None:
+    """A LoHa / LoKr / DoRA term under its kohya / LyCORIS keys — the only namespace that has names for all of them."""
+    if style != "kohya":
+        raise ValueError(f"{flat}: LoHa / LoKr / DoRA terms are written in the kohya style only, not {style!r}")
+    for n, t in term.factors.items():
+        t = t.contiguous()
+        if n == "lora_up" and term.factors["lora_down"].dim() == 4:
+            t = t.reshape(t.shape[0], t.shape[1], 1, 1)
+        out[f"{flat}.{n}" + (".weight" if n in ("lora_down", "lora_up") else "")] = t
+    if term.alpha is not None:
+        out[f"{flat}.alpha"] = torch.tensor(term.alpha)
+    if term.magnitude is not None:
+        conv = any(t.dim() == 4 for t in term.factors.values())
+        out[f"{flat}.dora_scale"] = term.magnitude.reshape(-1, 1, 1, 1) if conv else term.magnitude.reshape(-1, 1)

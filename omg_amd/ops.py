@@ -1662,3 +1662,84 @@ def image_prep(u8: torch.Tensor, out_hw: Tuple[int, int], resample: int, lut: Op
     L.check(lib.omg_image_resize_v(B, H, ow, oh, src.data_ptr(), pb, pc, ks, code, _p(lut), hp, wp, out.data_ptr(), _stream()),
             "omg_image_resize_v")
     return out if batched else out[0]
+
+
+# ------------------------------------------------------------------ LoRA bank build: weight-slot merge
+_LORA_KINDS = {"plain": L.LORA_PLAIN, "hada": L.LORA_HADA, "kron": L.LORA_KRON}
+
+
+def _lora_desc(term: dict, N: int, K: int) -> "L.LoraTermDesc":
+    """One term ``{"kind", "f", "s", "gain"}`` -> the C descriptor, shapes checked here so that the kernel reads inside its operands:
+    plain ``f = (up [N, r], down [r, K])``; hada ``f = (w1_a [N, r], w1_b [r, K], w2_a [N, r2], w2_b [r2, K])``; kron
+    ``f = (w1 [a, b], w2 [c, taps, d])`` with ``a c == N`` and ``taps b d == K``.  Factors are fp32, contiguous, on the device."""
+    kind, f = term["kind"], term["f"]
+    if kind not in _LORA_KINDS:
+        raise L.OmgHipError(f"unknown LoRA term kind {kind!r}")
+    for t in f:
+        _dev(t)
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise L.OmgHipError("LoRA term factors must be contiguous fp32 tensors")
+    d = L.LoraTermDesc()
+    d.kind, d.s = _LORA_KINDS[kind], float(term.get("s", 1.0))
+    if kind == "plain":
+        up, down = f
+        if up.dim() != 2 or down.dim() != 2 or up.shape[0] != N or down.shape[1] != K or up.shape[1] != down.shape[0] or up.shape[1] < 1:
+            raise L.OmgHipError(f"plain LoRA term: up {tuple(up.shape)} / down {tuple(down.shape)} do not give [{N}, {K}] (a zero-width stack is refused)")
+        d.r = up.shape[1]
+    elif kind == "hada":
+        a1, b1, a2, b2 = f
+        for a, b in ((a1, b1), (a2, b2)):
+            if a.dim() != 2 or b.dim() != 2 or a.shape[0] != N or b.shape[1] != K or a.shape[1] != b.shape[0] or a.shape[1] < 1:
+                raise L.OmgHipError(f"hada LoRA term: {tuple(a.shape)} . {tuple(b.shape)} does not give [{N}, {K}]")
+        d.r, d.r2 = a1.shape[1], a2.shape[1]
+    else:
+        w1, w2 = f
+        if w1.dim() != 2 or w2.dim() != 3 or w1.shape[0] * w2.shape[0] != N or w2.shape[1] * w1.shape[1] * w2.shape[2] != K or min(w1.shape + w2.shape) < 1:
+            raise L.OmgHipError(f"kron LoRA term: w1 {tuple(w1.shape)} (x) w2 [c, taps, d] {tuple(w2.shape)} does not give [{N}, {K}]")
+        d.a, d.b, d.c, d.taps, d.d = w1.shape[0], w1.shape[1], w2.shape[0], w2.shape[1], w2.shape[2]
+    for i, t in enumerate(f):
+        setattr(d, f"f{i}", t.data_ptr())
+    g = term.get("gain")
+    if g is not None:
+        _dev(g)
+        if g.dtype != torch.float32 or not g.is_contiguous() or tuple(g.shape) != (N,):
+            raise L.OmgHipError(f"LoRA term gain must be a contiguous fp32 [{N}]")
+        d.gain = g.data_ptr()
+    return d
+
+
+def _lora_w(w: torch.Tensor):
+    _dev(w)
+    if w.dim() != 2 or not w.is_contiguous() or w.shape[1] % 8 or w.shape[1] < 8 or w.shape[0] < 1:
+        raise L.OmgHipError(f"LoRA merge needs a contiguous 16-bit [N, K] weight with K a multiple of 8, got {tuple(w.shape)}")
+    return _dt(w), w.shape[0], w.shape[1]
+
+
+def lora_rownorm(w: torch.Tensor, term: dict) -> torch.Tensor:
+    """fp32 ``norm[n] = ||w[n, :] + s * delta[n, :]||_2`` of one term (omg_lora_rownorm): DoRA's weight norm, deterministic."""
+    dt, N, K = _lora_w(w)
+    d = _lora_desc(dict(term, gain=None), N, K)
+    out = torch.empty(N, dtype=torch.float32, device=w.device)
+    L.check(L.lib().omg_lora_rownorm(dt, N, K, w.data_ptr(), d, out.data_ptr(), _stream()), "omg_lora_rownorm")
+    return out
+
+
+def lora_merge_args(w: torch.Tensor, terms: Sequence[dict], out: torch.Tensor) -> "L.LoraMergeArgs":
+    """The checked argument block of one ``omg_lora_merge`` launch (the caller keeps ``w``, ``out`` and the terms' tensors alive)."""
+    dt, N, K = _lora_w(w)
+    _dev(out)
+    if out.dtype != w.dtype or tuple(out.shape) != (N, K) or not out.is_contiguous():
+        raise L.OmgHipError("lora_merge: out must be a contiguous [N, K] view of the weight's dtype")
+    if len(terms) > L.LORA_MAX_TERMS:
+        raise L.OmgHipError(f"lora_merge: {len(terms)} terms, at most {L.LORA_MAX_TERMS} per slot and layer")
+    a = L.LoraMergeArgs()
+    a.dtype, a.N, a.K, a.n_terms, a.W, a.out = dt, N, K, len(terms), w.data_ptr(), out.data_ptr()
+    for i, t in enumerate(terms):
+        a.terms[i] = _lora_desc(t, N, K)
+    return a
+
+
+def lora_merge(w: torch.Tensor, terms: Sequence[dict], out: torch.Tensor) -> None:
+    """``out[N, K] = round16(w * (1 + sum_t (gain_t - 1)) + sum_t gain_t * s_t * delta_t)`` (omg_lora_merge): one slot of a weight stack
+    from the 16-bit base and up to four term descriptors, all arithmetic in fp32, no dense delta in memory."""
+    L.check(L.lib().omg_lora_merge(lora_merge_args(w, terms, out), _stream()), "omg_lora_merge")

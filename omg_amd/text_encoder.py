@@ -104,7 +104,7 @@ class ClipTextEncoder(nn.Module):
 
     def set_lora(self, combo=None) -> None:
         """Activate text-encoder LoRA deltas for the following forwards: ``combo`` = [(weights, multiplier), ...] with
-        ``weights[module path] = (A [r, in], B [out, r])`` (``LoraAdapter.text_encoder[n]``) and multiplier =
+        ``weights[module path] = (A [r, in], B [out, r])`` or a ``LoraTerm`` (LoHa / LoKr) (``LoraAdapter.text_encoder[n]``) and multiplier =
         ``lora_scale * adapter_weight`` — PEFT's ``set_adapters`` + ``scale_lora_layers(text_encoder, lora_scale)`` as
         ``encode_prompt`` runs them (lora_pipeline.py:336-347).  The deltas are merged into the packed weight images in fp32
         (one rounding); ``None`` restores the base weights."""
@@ -121,8 +121,12 @@ class ClipTextEncoder(nn.Module):
         if not hits:
             return w
         acc = w.float()
-        for (a, b), m in hits:
-            acc = acc + m * (b.to(device=w.device, dtype=torch.float32) @ a.to(device=w.device, dtype=torch.float32))
+        for hit, m in hits:
+            if isinstance(hit, tuple):
+                a, b = hit
+                acc = acc + m * (b.to(device=w.device, dtype=torch.float32) @ a.to(device=w.device, dtype=torch.float32))
+            else:                               # a LoraTerm (LoHa / LoKr): the dense fp32 delta, formed on the host from the small factors
+                acc = acc + (m * hit.factor) * hit.dense().to(device=w.device)
         return acc.to(w.dtype)
 
     def _pack(self):
