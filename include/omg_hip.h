@@ -158,6 +158,14 @@ int omg_conv2d_mx8(const omg_conv2d_mx8_args* a, void* stream);
  * CrossAttnUpBlock2D/UpBlock2D — all inside the `self.unet(...)` call at
  * src/pipelines/lora_pipeline.py:546-566 (diffusers 0.25.0 unet_2d_blocks.py).
  * W is [Cout][ky][kx][C1+C2] (packed by the host from the diffusers OIHW key).
+ *
+ * upsample == 2, the phase form: the same result as upsample == 1 up to rounding, with 4/9 of the multiplies.  Four output pixels
+ * share each source pixel, so output pixel (2y+py, 2x+px) is a 2x2 convolution of the SOURCE image: tap (a, c), a, c in {0, 1},
+ * reads source pixel (y-1+py+a, x-1+px+c) (zeros outside the image) with the sum of the 1, 2, 2 or 4 original taps that land on
+ * it (py = 0: row y-1 with w[0], row y with w[1]+w[2]; py = 1: row y with w[0]+w[1], row y+1 with w[2]; the same along x).
+ * W is then the phase-packed weight [4 phases][Cout][4*C1], phase 2*py+px, taps (a, c) row-major, each summed weight rounded
+ * to the storage type once; the call is four launches of M = B*Hin*Win rows and K = 4*C1, each scattering its rows to its
+ * phase's output pixels.  Refused with OMG_EINVAL, never replaced by another form: stride != 1, ksize != 3, X2 / C2, residual.
  * ---------------------------------------------------------------------- */
 typedef struct {
   int32_t dtype;
@@ -166,9 +174,9 @@ typedef struct {
   int32_t Hout, Wout, Cout;   /* Cout % 8 == 0                                        */
   int32_t ksize;              /* 1 or 3                                               */
   int32_t stride;             /* 1 or 2                                               */
-  int32_t upsample;           /* 1: conv runs on nearest-2x-upsampled input           */
+  int32_t upsample;           /* 1: conv runs on nearest-2x-upsampled input; 2: the same as four 2x2 phase convolutions (above) */
   const void* X1; const void* X2;
-  const void* W;              /* [Cout][ksize*ksize*(C1+C2)]                           */
+  const void* W;              /* [Cout][ksize*ksize*(C1+C2)]; upsample == 2: [4][Cout][4*C1] */
   const void* bias;           /* [Cout] or NULL                                       */
   const void* group_bias; int64_t ldgb; /* [B, Cout] per-sample bias (time emb) or NULL */
   const void* residual;       /* NHWC [B,Hout,Wout,Cout] or NULL                      */
@@ -197,6 +205,8 @@ int omg_conv2d(const omg_conv2d_args* a, void* stream);
  *                 A2 = the down result, W2 = [S][Cout][K2] = s*B: samples with slot >= 0 add A2 . W2[slot]^T into the SAME
  *                 accumulator before the epilogue (acc + bias + group_bias) * out_scale + residual, with the activation.
  * Without group_adapter every sample uses slot 0.  Slot values are read on the device and not range-checked.
+ * conv.upsample == 2 (the phase form of omg_conv2d): every slot holds the phase image [4][Cout][4*C1] (w_slot_stride >= 4*Cout*4*C1
+ * or 0); the LoRA K-segment (K2 > 0) is refused.
  * ---------------------------------------------------------------------- */
 typedef struct {
   omg_conv2d_args conv;            /* exactly omg_conv2d's meaning                                  */

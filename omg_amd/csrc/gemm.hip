@@ -70,7 +70,7 @@ OMG_DEV void acc_init_cols(const GemmP& p, f32x16 (&acc)[MT][NT], int l31, int c
   }
 }
 
-template <typename T>
+template <typename T, bool PH = false>
 OMG_DEV void gemm_epilogue(const GemmP& p, f32x16 (&acc)[2][2], char* smem, int w, int lane, int m0, int n0, int m_end) {
   const int hi = lane >> 5, l31 = lane & 31;
   const int wm = w >> 1, wn = w & 1;
@@ -145,7 +145,9 @@ OMG_DEV void gemm_epilogue(const GemmP& p, f32x16 (&acc)[2][2], char* smem, int 
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] *= p.out_scale;
         }
-        *(u32x4*)(p.C + ((long)gm * p.ldc + gc) * 2) = pack8<T>(v);
+        int orow = gm;
+        if constexpr (PH) orow = phase_out_row(p, gm);
+        *(u32x4*)(p.C + ((long)orow * p.ldc + gc) * 2) = pack8<T>(v);
       }
     }
   }
@@ -153,174 +155,17 @@ OMG_DEV void gemm_epilogue(const GemmP& p, f32x16 (&acc)[2][2], char* smem, int 
 
 // CSEG (CONV only): the launch may carry the LoRA second K-segment (omg_conv2d_slots): stages kt >= nk1 read plain A2 rows and W2p exactly
 // as the non-conv form does.  A separate instantiation, so that the conv kernels omg_conv2d launches keep their code.
-template <typename T, bool CONV, bool GLDS, bool CSEG = false>
-__global__ __launch_bounds__(256, 2) void gemm_kernel(GemmP p) {
-  static_assert(CONV || !CSEG, "CSEG is the segment of the CONV form; the plain form always has it");
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int hi = lane >> 5;
-  const int l31 = lane & 31;
-
-  // ---- tile mapping: XCD-aware bijective remap, then M-fastest within the chunk
-  const int nwg = gridDim.x;
-  int bid = blockIdx.x;
-  {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  const int tiles_per_group = p.tiles_m * p.tiles_n;
-  const int grp = bid / tiles_per_group;
-  const int t_in = bid - grp * tiles_per_group;
-  // grouped ordering: 8 M-tiles x all N-tiles per group, M fastest inside the group, so that the ~32 consecutive
-  // tiles an XCD receives touch ~8 A panels + <= 4..5 W panels instead of 32 + 1 (tall-skinny GEMMs re-read A per N tile)
-  int tm, tn;
-  {
-    const int per_group = 8 * p.tiles_n;
-    const int gid = t_in / per_group;
-    const int first_m = gid * 8;
-    const int gsz = (p.tiles_m - first_m) < 8 ? (p.tiles_m - first_m) : 8;
-    const int r = t_in - gid * per_group;
-    tm = first_m + (r % gsz);
-    tn = r / gsz;
-  }
-  const int m_base = (p.tile_groups > 1) ? grp * p.rows_per_group : 0;
-  const int m_end = (p.tile_groups > 1) ? m_base + p.rows_per_group : p.M;
-  const int m0 = m_base + tm * BM;
-  const int n0 = tn * BN;
-
-  int adapter = 0;
-  if (p.group_adapter != nullptr) adapter = p.group_adapter[grp];
-  const bool seg2 = (p.K2 > 0) && (adapter >= 0);
-  if (p.w_adapter_stride != 0 && adapter < 0) return;   // LoRA-down GEMM for a sample without adapter
-  const char* Wp = p.W + (p.w_adapter_stride != 0 ? (long)adapter * p.w_adapter_stride * 2 : 0);
-  const char* W2p = p.W2 + (seg2 ? (long)adapter * p.w2_adapter_stride * 2 : 0);
-  const int a2off = (p.a2_col_block > 0) ? (n0 / p.a2_col_block) * p.K2 : 0;
-
-  const int nk1 = (p.K + BK - 1) / BK;
-  const int nk2 = seg2 ? (p.K2 + BK - 1) / BK : 0;
-  const int nk = nk1 + nk2;
-
-  // ---- per-lane staging coordinates: 4 A rows + 4 W rows per k-tile
-  const int prow = lane >> 3;          // row within the 8-row DMA piece
-  const int ppos = lane & 7;           // 16-B position within the 128-B row
-  int arow[4];                         // global A row (clamped)
-  int wrow[4];                         // global W row (clamped)
-  int cb[4], cy[4], cx[4];             // conv: decoded output pixel
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int r = w * 32 + i * 8 + prow;
-    int gm = m0 + r; if (gm > m_end - 1) gm = m_end - 1;
-    int gn = n0 + r; if (gn > p.N - 1) gn = p.N - 1;
-    arow[i] = gm; wrow[i] = gn;
-    if constexpr (CONV) {
-      const int hw = p.Hout * p.Wout;
-      const int b = gm / hw; const int rem = gm - b * hw;
-      cb[i] = b; cy[i] = rem / p.Wout; cx[i] = rem - cy[i] * p.Wout;
-    }
-  }
-  const int Ctot = p.C1 + p.C2;
-  const int cpt = CONV ? Ctot / BK : 1;   // k-tiles per tap
-  const int pad = CONV ? (p.ksize == 3 ? 1 : 0) : 0;
-  const char* zero = (const char*)omg_zero_page;
-
-  u32x4 hold[8];
-  char* ldsA = smem;
-  char* ldsB = smem + 2 * TILE_BYTES;
-
-  auto issue = [&](int kt, int buf) {
-    const bool s2 = kt >= nk1;
-    const int k0 = (s2 ? kt - nk1 : kt) * BK;
-    const int Kseg = s2 ? p.K2 : p.K;
-    // conv tap decode (wave-uniform)
-    int dy = 0, dx = 0, c0 = k0;
-    const char* xsrc = p.A; int xC = p.C1;
-    if constexpr (CONV) {
-      const int ktc = (CSEG && s2) ? 0 : kt;                   // a segment stage decodes no tap
-      const int tap = ktc / cpt; const int cc = ktc - tap * cpt;
-      dy = tap / p.ksize; dx = tap - dy * p.ksize;
-      c0 = cc * BK;
-      if (c0 >= p.C1) { xsrc = p.X2; xC = p.C2; c0 -= p.C1; }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int r = w * 32 + i * 8 + prow;
-      const int c = ppos ^ ((r >> 1) & 7);                    // source chunk for this LDS position
-      const bool kvalid = (k0 + c * 8) < Kseg;
-      // A operand
-      const char* asrc;
-      if constexpr (CONV) {
-        int iy = cy[i] * p.stride + dy - pad;
-        int ix = cx[i] * p.stride + dx - pad;
-        const int Hl = p.upsample ? p.Hin * 2 : p.Hin;
-        const int Wl = p.upsample ? p.Win * 2 : p.Win;
-        const bool ok = (iy >= 0) && (iy < Hl) && (ix >= 0) && (ix < Wl);
-        if (p.upsample) { iy >>= 1; ix >>= 1; }
-        const long pix = ((long)cb[i] * p.Hin + iy) * p.Win + ix;
-        asrc = ok ? xsrc + (pix * xC + c0 + c * 8) * 2 : zero;
-        if constexpr (CSEG) {
-          if (s2) asrc = kvalid ? p.A2 + ((long)arow[i] * p.lda2 + k0 + c * 8) * 2 : zero;
-        }
-      } else {
-        if (!s2) asrc = kvalid ? p.A + ((long)arow[i] * p.lda + k0 + c * 8) * 2 : zero;
-        else     asrc = kvalid ? p.A2 + ((long)arow[i] * p.lda2 + a2off + k0 + c * 8) * 2 : zero;
-      }
-      stage16<GLDS>(asrc, ldsA + buf * TILE_BYTES + (w * 32 + i * 8) * 128, lane, hold[i]);
-      // W operand
-      const char* wsrc;
-      if (!s2) wsrc = kvalid ? Wp + ((long)wrow[i] * p.ldw + (CONV ? kt * BK : k0) + c * 8) * 2 : zero;
-      else     wsrc = kvalid ? W2p + ((long)wrow[i] * p.ldw2 + k0 + c * 8) * 2 : zero;
-      stage16<GLDS>(wsrc, ldsB + buf * TILE_BYTES + (w * 32 + i * 8) * 128, lane, hold[4 + i]);
-    }
-  };
-  auto commit = [&](int buf) {   // register-staged fallback: write the held chunks
-    if constexpr (!GLDS) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int off = (w * 32 + i * 8) * 128 + lane * 16;
-        *(u32x4*)(ldsA + buf * TILE_BYTES + off) = hold[i];
-        *(u32x4*)(ldsB + buf * TILE_BYTES + off) = hold[4 + i];
-      }
-    }
-  };
-
-  const int wm = w >> 1, wn = w & 1;
-  f32x16 acc[2][2];
-  acc_init_cols<T, 2, 2>(p, acc, lane & 31, n0 + wn * 64, m0);
-
-  using V8 = typename Vec<T>::v8;
-
-  issue(0, 0);
-  commit(0);
-  for (int kt = 0; kt < nk; ++kt) {
-    const int buf = kt & 1;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (kt + 1 < nk) issue(kt + 1, buf ^ 1);
-    const char* a_base = ldsA + buf * TILE_BYTES;
-    const char* b_base = ldsB + buf * TILE_BYTES;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      V8 af[2], bf[2];
-      const int kc = ks * 2 + hi;
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int ra = wm * 64 + i * 32 + l31;
-        af[i] = *(const V8*)(a_base + ra * 128 + ((kc ^ ((ra >> 1) & 7)) << 4));
-        const int rb = wn * 64 + i * 32 + l31;
-        bf[i] = *(const V8*)(b_base + rb * 128 + ((kc ^ ((rb >> 1) & 7)) << 4));
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = Vec<T>::mfma32(af[i], bf[j], acc[i][j]);
-    }
-    if constexpr (!GLDS) { if (kt + 1 < nk) commit(buf ^ 1); }
-  }
-
-  gemm_epilogue<T>(p, acc, smem, w, lane, m0, n0, m_end);
-}
+// gemm_phase_kernel (CONV only, never with CSEG): the same text compiled as a phase launch (gemm_tile128.inc).
+#define OMG_TILE128_KERNEL gemm_kernel
+#define OMG_TILE128_PH false
+#include "gemm_tile128.inc"
+#undef OMG_TILE128_KERNEL
+#undef OMG_TILE128_PH
+#define OMG_TILE128_KERNEL gemm_phase_kernel
+#define OMG_TILE128_PH true
+#include "gemm_tile128.inc"
+#undef OMG_TILE128_KERNEL
+#undef OMG_TILE128_PH
 
 
 // ------------------------------------------------------------------------------------------------
@@ -991,6 +836,29 @@ int launch(const GemmP& p, hipStream_t s) {
   return omg_check_launch("gemm");
 }
 
+// One phase of omg_conv2d's upsample == 2 form.  Two kernels only: the 256x320 tile where the chooser picks it, the 128x128 kernel for
+// everything else (small and ragged shapes, operands >= 2 GiB) — both give the same bits, so the choice never shows in a result.
+template <typename T>
+int launch_phase(const GemmP& p, hipStream_t s) {
+  const int mrows = p.tile_groups > 1 ? p.rows_per_group : p.M;
+  if (g_use_glds) {
+    const int v = choose_variant(mrows, p.tile_groups, p.N, true);
+    const long lim = 0x7fff0000L;
+    const long a_sz = (long)p.M * p.C1 * 2, c_sz = 4L * p.M * p.ldc * 2;
+    const bool ok = a_sz < lim && (long)p.N * p.ldw * 2 < lim && c_sz < lim &&
+                    (p.group_bias == nullptr || (long)(p.M / p.rows_per_group + 1) * p.ldgb * 2 < lim);
+    if (v == 28 && ok) return launch_v13_phase<T>(p, s, mrows);
+  }
+  const int grid = p.tile_groups * p.tiles_m * p.tiles_n;
+  if (grid <= 0) return OMG_OK;
+  if (g_use_glds) {
+    OMG_LAUNCH((gemm_phase_kernel<T, true, true>), dim3(grid), dim3(256), LDS_BYTES, s, p);
+  } else {
+    OMG_LAUNCH((gemm_phase_kernel<T, true, false>), dim3(grid), dim3(256), LDS_BYTES, s, p);
+  }
+  return omg_check_launch("gemm");
+}
+
 bool g_attr_set = false;
 void ensure_attrs() {
   if (g_attr_set) return;
@@ -1002,6 +870,8 @@ void ensure_attrs() {
   (void)hipFuncSetAttribute((const void*)gemm_kernel<f16, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
   (void)hipFuncSetAttribute((const void*)gemm_kernel<f16, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
   (void)hipFuncSetAttribute((const void*)gemm_kernel<f16, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+  (void)hipFuncSetAttribute((const void*)gemm_phase_kernel<f16, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+  (void)hipFuncSetAttribute((const void*)gemm_phase_kernel<f16, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
 #ifndef OMG_DEV_F16_ONLY
   (void)hipFuncSetAttribute((const void*)gemm_kernel<bf16, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
   (void)hipFuncSetAttribute((const void*)gemm_kernel<bf16, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
@@ -1009,6 +879,8 @@ void ensure_attrs() {
   (void)hipFuncSetAttribute((const void*)gemm_kernel<bf16, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
   (void)hipFuncSetAttribute((const void*)gemm_kernel<bf16, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
   (void)hipFuncSetAttribute((const void*)gemm_kernel<bf16, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+  (void)hipFuncSetAttribute((const void*)gemm_phase_kernel<bf16, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+  (void)hipFuncSetAttribute((const void*)gemm_phase_kernel<bf16, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
 #endif
 }
 
@@ -1076,7 +948,11 @@ static int conv2d_params(const omg_conv2d_args* a, GemmP& p) {
   OMG_REQUIRE(a->C1 > 0 && a->C1 % 64 == 0 && a->C2 % 64 == 0 && a->C2 >= 0, "omg_conv2d: channels must be multiples of 64");
   OMG_REQUIRE(a->Cout % 8 == 0, "omg_conv2d: Cout % 8");
   OMG_REQUIRE(a->X1 && a->W && a->Y && (a->C2 == 0 || a->X2), "omg_conv2d: null operand");
+  OMG_REQUIRE(a->upsample >= 0 && a->upsample <= 2, "omg_conv2d: upsample must be 0, 1 or 2");
   OMG_REQUIRE(!(a->upsample && a->stride != 1), "omg_conv2d: upsample with stride");
+  const bool phase = a->upsample == 2;
+  if (phase) OMG_REQUIRE(a->ksize == 3 && a->C2 == 0 && a->X2 == nullptr && a->residual == nullptr,
+                         "omg_conv2d: the phase form (upsample == 2) is the 3x3 convolution of one input without residual");
   const int Hl = a->upsample ? 2 * a->Hin : a->Hin, Wl = a->upsample ? 2 * a->Win : a->Win;
   const int pad = a->ksize == 3 ? 1 : 0;
   OMG_REQUIRE(a->Hout == (Hl + 2 * pad - a->ksize) / a->stride + 1 && a->Wout == (Wl + 2 * pad - a->ksize) / a->stride + 1,
@@ -1094,6 +970,11 @@ static int conv2d_params(const omg_conv2d_args* a, GemmP& p) {
   p.act = a->act; p.out_scale = a->out_scale; p.C = (char*)a->Y; p.ldc = a->Cout;
   p.Hin = a->Hin; p.Win = a->Win; p.C1 = a->C1; p.C2 = a->C2; p.Hout = a->Hout; p.Wout = a->Wout;
   p.ksize = a->ksize; p.stride = a->stride; p.upsample = a->upsample;
+  if (phase) {      // one phase's problem on the source grid (GemmP); W and the phase id are set per launch by conv2d_launch
+    p.M = a->B * a->Hin * a->Win; p.K = 4 * a->C1; p.ldw = p.K;
+    p.rows_per_group = a->Hin * a->Win;
+    p.Hout = a->Hin; p.Wout = a->Win; p.ksize = 2; p.upsample = 0;
+  }
   p.tiles_m = (p.M + BM - 1) / BM; p.tiles_n = (p.N + BN - 1) / BN;
   if (a->group_bias) OMG_REQUIRE(a->ldgb % 8 == 0, "omg_conv2d: ldgb");
 #ifdef OMG_DEV_F16_ONLY
@@ -1102,7 +983,21 @@ static int conv2d_params(const omg_conv2d_args* a, GemmP& p) {
   return OMG_OK;
 }
 
-static int conv2d_launch(int dtype, const GemmP& p, hipStream_t s) {
+static int conv2d_launch(int dtype, const GemmP& p, hipStream_t s, bool phase = false) {
+  if (phase) {      // four launches, phase 2 py + px against image `phase` of W = [4][Cout][4 Cin] (per slot, where there are slots)
+    GemmP q = p;
+    for (int ph = 0; ph < 4; ++ph) {
+      q.W = p.W + (long)ph * p.N * p.K * 2;
+      q.upsample = ph;
+#ifdef OMG_DEV_F16_ONLY
+      const int rc = launch_phase<f16>(q, s);
+#else
+      const int rc = dtype == OMG_F16 ? launch_phase<f16>(q, s) : launch_phase<bf16>(q, s);
+#endif
+      if (rc != OMG_OK) return rc;
+    }
+    return OMG_OK;
+  }
 #ifdef OMG_DEV_F16_ONLY
   (void)dtype;
   return launch<f16, true>(p, s);
@@ -1116,7 +1011,7 @@ extern "C" int omg_conv2d(const omg_conv2d_args* a, void* stream) {
   GemmP p{};
   const int rc = conv2d_params(a, p);
   if (rc != OMG_OK || p.M == 0) return rc;
-  return conv2d_launch(a->dtype, p, (hipStream_t)stream);
+  return conv2d_launch(a->dtype, p, (hipStream_t)stream, a->upsample == 2);
 }
 
 // omg_conv2d with a weight slot per sample and the LoRA second K-segment (include/omg_hip.h).  A sample is a tile group
@@ -1136,7 +1031,9 @@ extern "C" int omg_conv2d_slots(const omg_conv2d_slots_args* a, void* stream) {
   GemmP p{};
   const int rc = conv2d_params(&a->conv, p);
   if (rc != OMG_OK) return rc;
-  OMG_REQUIRE(a->w_slot_stride == 0 || a->w_slot_stride >= (int64_t)p.N * p.K, "omg_conv2d_slots: w_slot_stride smaller than one weight");
+  const bool phase = a->conv.upsample == 2;
+  OMG_REQUIRE(!(phase && a->K2 > 0), "omg_conv2d_slots: the phase form (upsample == 2) takes no LoRA segment");
+  OMG_REQUIRE(a->w_slot_stride == 0 || a->w_slot_stride >= (int64_t)p.N * p.K * (phase ? 4 : 1), "omg_conv2d_slots: w_slot_stride smaller than one weight");
   if (p.M == 0) return OMG_OK;
   const bool per_sample = a->group_adapter != nullptr && a->conv.B > 1;
   if (per_sample) {
@@ -1148,5 +1045,5 @@ extern "C" int omg_conv2d_slots(const omg_conv2d_slots_args* a, void* stream) {
   p.A2 = (const char*)a->A2; p.lda2 = a->lda2; p.W2 = (const char*)a->W2; p.ldw2 = a->ldw2;
   p.K2 = a->K2; p.w2_adapter_stride = a->w2_slot_stride;
   if (p.K2 == 0) { p.A2 = nullptr; p.W2 = nullptr; }
-  return conv2d_launch(a->conv.dtype, p, (hipStream_t)stream);
+  return conv2d_launch(a->conv.dtype, p, (hipStream_t)stream, phase);
 }

@@ -21,7 +21,8 @@ struct GemmP {
   const char* residual; long ldr;
   int act; float out_scale;
   char* C; long ldc;
-  // conv geometry (CONV only)
+  // conv geometry (CONV only).  A phase launch (the PH instantiations: one of the four 2x2 convolutions a nearest-2x upsample + 3x3 splits
+  // into) runs on the SOURCE grid: Hout = Hin, Wout = Win, ksize = 2, stride = 1, and `upsample` carries the phase id 2 py + px
   int Hin, Win, C1, C2, Hout, Wout, ksize, stride, upsample;
   const char* X2;
   int tiles_m, tiles_n;              // tiles_m is per group
@@ -42,6 +43,13 @@ typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
 // multiple of 256, i.e. no tile of any variant straddles samples), the K loop adds the products in the same order, and
 // the epilogue is [+ per-row group bias if it was not folded] -> SiLU (hardware reciprocal) -> fma(v, out_scale, residual).
 OMG_DEV bool fold_group_bias(const GemmP& p) { return p.group_bias != nullptr && p.rows_per_group % 256 == 0; }
+
+// Phase launch: GEMM row m = (b Hin + y) Win + x is source pixel (y, x) of sample b; its result is output pixel (2 y + py, 2 x + px) of the
+// [B, 2 Hin, 2 Win] image, i.e. output row ((m / Win) 2 + py) 2 Win + 2 (m % Win) + px.  Everything else of a row (bias, per-sample bias) is indexed by m.
+OMG_DEV int phase_out_row(const GemmP& p, int m) {
+  const int q = m / p.Win;
+  return ((2 * q + (p.upsample >> 1)) * p.Win + (m - q * p.Win)) * 2 + (p.upsample & 1);
+}
 
 template <int N> OMG_DEV void wait_vmcnt() {
   static_assert(N >= 0 && N <= 63, "vmcnt range");
@@ -193,7 +201,7 @@ OMG_DEV void xe_put(const EpiCtx<4>& cx, int piece, const float (&v)[8]) {
   *(u32x2*)(b + (c0 << 4)) = r0;
   *(u32x2*)(b + ((c0 ^ 1) << 4)) = r1;
 }
-template <typename T, int ROWB>
+template <typename T, int ROWB, bool PH = false>
 OMG_DEV void xe_flush(const GemmP& p, const EpiCtx<4>& cx, int i, int col0) {
   constexpr int LPR = ROWB / 16;                    // lanes per row: 16 (256-byte rows) or 8 (GEGLU: 128-byte rows)
   constexpr int RPI = 64 / LPR;                     // rows per store instruction
@@ -242,7 +250,9 @@ OMG_DEV void xe_flush(const GemmP& p, const EpiCtx<4>& cx, int i, int col0) {
 #pragma unroll
   for (int u = 0; u < NU; ++u) {
     const int gm = cx.wm0 + i * 32 + u * RPI + rq;
-    const int off = (gm < cx.m_end && col_ok) ? gm * (int)p.ldc * 2 + colb : EPI_OOB;
+    int orow = gm;
+    if constexpr (PH) orow = phase_out_row(p, gm);
+    const int off = (gm < cx.m_end && col_ok) ? orow * (int)p.ldc * 2 + colb : EPI_OOB;
     __builtin_amdgcn_raw_buffer_store_b128(d[u], cx.rsC, off, 0, 2);            // nt: stream past L2
   }
   asm volatile("" ::: "memory");

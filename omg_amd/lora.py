@@ -302,6 +302,9 @@ class LoraBank:
                         for l in projs:
                             if l.w_slots is None:
                                 l.w_slots = l.weight.data.unsqueeze(0).repeat(1 + len(self.slots), 1, 1).contiguous()
+            for m in self.unet.modules():      # the phase images of the new conv slots, here and not inside a captured forward
+                if isinstance(m, Conv2d) and m.upsamples and m.w_slots is not None and m._phase_form(True, None, None):
+                    m.slot_phase_weight()
         self.version += 1
         self._invalidate_packed()
 
@@ -373,6 +376,7 @@ class LoraBank:
             elif isinstance(m, Conv2d):
                 had_conv |= m.has_lora_slots()
                 m.lora_down = m.lora_up = m.w_slots = None
+                m.drop_slot_phase()
         if had_conv:      # captured graphs hold the freed conv stacks' pointers (and, in fp8 mode, took the other kernel)
             bump_pointer_epoch()
         self._invalidate_packed()

@@ -213,6 +213,11 @@ class GEGLU(_Packed):
 class Conv2d(_Packed):
     """3x3 (pad 1) or 1x1 conv on NHWC activations; canonical weight is diffusers' OIHW."""
 
+    # ``forward(upsample=True)`` of a 16-bit 3x3 / stride 1 convolution runs as four 2x2 phase convolutions on the source image
+    # (``ops.conv2d(upsample=2)``: 4/9 of the multiplies).  False forces the direct form (all nine taps on the upsampled grid), on the
+    # class or on one instance — what the tests compare the phase form with.
+    phase_upsample = True
+
     def __init__(self, cin: int, cout: int, ksize: int, stride: int = 1, dtype=torch.float16, device=None):
         super().__init__()
         self.cin, self.cout, self.ksize, self.stride = cin, cout, ksize, stride
@@ -226,6 +231,8 @@ class Conv2d(_Packed):
         # merged mode: [1 + slots, cout, k*k*cin] = base weight followed by W + scale * B_s A_s per slot
         self.w_slots: Optional[torch.Tensor] = None
         self.lora_state: Optional[LoraState] = None   # set per forward by the UNet
+        self.upsamples = False    # set by the owner of a conv it calls with ``upsample=True``: LoraBank.build then builds the slots' phase image
+        self._slot_phase = None   # (the ``w_slots`` it was built from, [1 + slots, 4, cout, 4 * cin]): see ``slot_phase_weight``
 
     def lora_eligible(self) -> bool:
         """Whether the slot kernel (omg_conv2d_slots) can run this conv with a LoRA: 16-bit storage (not the fp32 VAE convs), input
@@ -239,6 +246,41 @@ class Conv2d(_Packed):
         if "w" not in self._packed:
             self._packed["w"] = ops.pack_conv_weight(self.weight.data)
         return self._packed["w"]
+
+    def phase_weight(self) -> torch.Tensor:
+        """Phase image [4, cout, 4 * cin] of a 3x3 weight (``ops.pack_conv_weight_phase``); cached and invalidated like the packed weight."""
+        if "wp" not in self._packed:
+            if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+                raise L.OmgHipError("the phase image of a convolution weight must be built before a graph is captured (run the forward once eagerly)")
+            self._packed["wp"] = ops.pack_conv_weight_phase(self.weight.data)
+        return self._packed["wp"]
+
+    def slot_phase_weight(self) -> torch.Tensor:
+        """Phase image of ``w_slots`` (every slot its own [4, cout, 4 * cin] image).  It belongs to ONE ``w_slots`` tensor: ``LoraBank.build``
+        calls this for the convs marked ``upsamples`` right after it replaced the slots, any other conv builds it at its first eager
+        ``forward(upsample=True)``; a replaced or cleared ``w_slots`` drops it, and the pointer epoch moves with it (captured graphs
+        hold its pointer)."""
+        if self._slot_phase is not None and self._slot_phase[0] is self.w_slots:
+            return self._slot_phase[1]
+        self.drop_slot_phase()
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise L.OmgHipError("the phase image of the weight slots must be built before a graph is captured")
+        s = self.w_slots
+        oihw = s.view(s.shape[0], self.cout, 3, 3, self.cin).permute(0, 1, 4, 2, 3)
+        self._slot_phase = (s, ops.pack_conv_weight_phase(oihw))
+        return self._slot_phase[1]
+
+    def drop_slot_phase(self) -> None:
+        if self._slot_phase is not None:
+            self._slot_phase = None
+            bump_pointer_epoch()
+
+    def _phase_form(self, upsample, x2, residual) -> bool:
+        """The ONE rule for the phase form: the layer and the call's operands, never the batch or the image size (a row's arithmetic must
+        be the same at every M: batched == single, graph == eager, dedup == full) — and never whether the layer carries LoRA stacks:
+        a sample without adapter must come out of the plain, the merged and the segment call with the same bits, and an adapter whose
+        conv factors are zero must give the bits of an adapter without conv entries."""
+        return bool(upsample) and self.phase_upsample and self.ksize == 3 and self.stride == 1 and x2 is None and residual is None
 
     def wino_weight(self) -> Optional[torch.Tensor]:
         """Winograd F(2x2, 3x3) image of an fp32 3x3 weight (ops.conv2d_f32, algo "auto"); cached and invalidated like the packed weight."""
@@ -276,10 +318,14 @@ class Conv2d(_Packed):
             return ops.conv2d_f32(x, self.packed_weight(), self.ksize, upsample=upsample, bias=self.bias, residual=residual,
                                   wu=self.wino_weight())
         st = self.lora_state
+        phase = self._phase_form(upsample, x2, residual)
         if st is not None and self.has_lora_slots():
             if x.shape[0] != st.groups:
                 raise L.OmgHipError("LoRA groups do not match the batch of the convolution")
             if st.merged and self.w_slots is not None:      # one conv, a weight slot per sample
+                if phase:
+                    return ops.conv2d(x, self.slot_phase_weight(), 3, upsample=2, bias=self.bias, group_bias=group_bias,
+                                      w_group_adapter=st.group_adapter)
                 return ops.conv2d(x, self.w_slots, self.ksize, stride=self.stride, upsample=upsample, x2=x2, bias=self.bias,
                                   group_bias=group_bias, residual=residual, w_group_adapter=st.group_adapter)
             if not st.merged and self.lora_down is not None:
@@ -288,8 +334,19 @@ class Conv2d(_Packed):
                 # `t` is torch.empty: the rows of a sample whose slot is -1 are never written (the down launch skips it) and never read
                 # (the segment of the base conv below is off for that sample)
                 t = ops.conv2d(x, self.lora_down, self.ksize, stride=self.stride, upsample=upsample, x2=x2, w_group_adapter=st.group_adapter)
+                if phase:
+                    # The phase form takes no K-segment (a phase launch's rows are source pixels, the segment's are output pixels): the
+                    # base conv runs its phases, then the 1x1 up conv adds t . up[slot]^T onto the samples that have an adapter, in
+                    # place (a sample is a group; slot -1 is skipped and keeps the plain conv's bits).  One more rounding than the
+                    # segment's single accumulator, on these layers only; the down conv keeps the direct taps.
+                    y = ops.conv2d(x, self.phase_weight(), 3, upsample=2, bias=self.bias, group_bias=group_bias)
+                    y2 = y.view(-1, self.cout)
+                    ops.gemm(t.view(y2.shape[0], -1), self.lora_up, residual=y2, out=y2, groups=x.shape[0], w_group_adapter=st.group_adapter)
+                    return y
                 return ops.conv2d(x, self.packed_weight(), self.ksize, stride=self.stride, upsample=upsample, x2=x2, bias=self.bias,
                                   group_bias=group_bias, residual=residual, lora=ops.LoraSpec(t, self.lora_up, st.group_adapter))
+        if phase:
+            return ops.conv2d(x, self.phase_weight(), 3, upsample=2, bias=self.bias, group_bias=group_bias)
         return ops.conv2d(x, self.packed_weight(), self.ksize, stride=self.stride, upsample=upsample, x2=x2, bias=self.bias,
                           group_bias=group_bias, residual=residual)
 

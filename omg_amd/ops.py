@@ -247,12 +247,16 @@ def gemm_mx8(a: Mx8Tensor, w: Mx8Tensor, *, out_dtype: torch.dtype = torch.float
     return oq if oq is not None else out
 
 
-def conv2d(x1: torch.Tensor, w: torch.Tensor, ksize: int, *, stride: int = 1, upsample: bool = False,
+def conv2d(x1: torch.Tensor, w: torch.Tensor, ksize: int, *, stride: int = 1, upsample: "bool | int" = False,
            x2: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
            group_bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
            out_scale: float = 1.0, act: int = L.ACT_NONE, w_group_adapter: Optional[torch.Tensor] = None,
            lora: Optional[LoraSpec] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """NHWC implicit-GEMM conv; ``w`` is ``[Cout, ksize*ksize*(C1+C2)]`` (see pack_conv_weight).
+
+    ``upsample``: False / True (the convolution of the nearest-2x upsampled input, all nine taps), or 2 — the same convolution as four
+    2x2 phase convolutions on the source image (4/9 of the multiplies; ``w`` from :func:`pack_conv_weight_phase`; equal to
+    ``upsample=True`` up to one rounding of the summed weights and the order of the fp32 accumulation).
 
     LoRA on convolutions (``omg_conv2d_slots``): ``w`` may be 3-D ``[slots, Cout, K]`` together with ``w_group_adapter`` (int32
     device tensor, one weight slot per sample; a sample with slot -1 is skipped and its rows of ``out`` stay as they are) — the
@@ -268,9 +272,17 @@ def conv2d(x1: torch.Tensor, w: torch.Tensor, ksize: int, *, stride: int = 1, up
     if x2 is not None:
         assert x2.is_contiguous() and x2.shape[:3] == x1.shape[:3]
         C2 = x2.shape[3]
-    slots = w.dim() == 3 or w_group_adapter is not None or lora is not None
+    phase = int(upsample) == 2
     Cout = w.shape[-2]
-    assert w.is_contiguous() and w.shape[-1] == ksize * ksize * (C1 + C2)
+    if phase:
+        # the four 2x2 phase convolutions on the source image: ``w`` is pack_conv_weight_phase's [4, Cout, 4 * C1] ([slots, 4, Cout, 4 * C1])
+        if ksize != 3 or stride != 1 or x2 is not None or lora is not None or residual is not None:
+            raise L.OmgHipError("the phase form (upsample=2) is the 3x3 / stride 1 convolution of one input without residual or LoRA segment")
+        assert w.is_contiguous() and w.dim() in (3, 4) and tuple(w.shape[-3:]) == (4, Cout, 4 * C1)
+        slots = w.dim() == 4 or w_group_adapter is not None
+    else:
+        slots = w.dim() == 3 or w_group_adapter is not None or lora is not None
+        assert w.is_contiguous() and w.shape[-1] == ksize * ksize * (C1 + C2)
     Hl, Wl = (2 * Hin, 2 * Win) if upsample else (Hin, Win)
     pad = 1 if ksize == 3 else 0
     Hout = (Hl + 2 * pad - ksize) // stride + 1
@@ -298,7 +310,7 @@ def conv2d(x1: torch.Tensor, w: torch.Tensor, ksize: int, *, stride: int = 1, up
     k2 = 0
     if slots:
         adapter = w_group_adapter
-        sa.w_slot_stride = w.stride(0) if w.dim() == 3 else 0
+        sa.w_slot_stride = w.stride(0) if w.dim() == (4 if phase else 3) else 0
         if lora is not None:
             a2, w2 = lora.a2, lora.w2
             a2 = a2.reshape(-1, a2.shape[-1])
@@ -320,6 +332,9 @@ def conv2d(x1: torch.Tensor, w: torch.Tensor, ksize: int, *, stride: int = 1, up
     if _PROF is not None:
         t0 = _PROF.begin()
         L.check(fn(C.byref(arg), _stream()), what)
+        if phase:       # the executed work: the call's four launches of M = B Hin Win rows and K = 4 C1 in one record, under one launch's shape
+            _PROF.end("gemm", 2.0 * 4 * B * Hin * Win * Cout * 4 * C1, t0, ("conv", B * Hin * Win, Cout, 4 * C1, 0, B if slots else 1, "x4 phases"))
+            return y
         K = ksize * ksize * (C1 + C2)
         _PROF.end("gemm", 2.0 * B * Hout * Wout * Cout * (K + k2), t0, ("conv", B * Hout * Wout, Cout, K, k2, B if slots else 1, 0))
         return y
@@ -1552,6 +1567,28 @@ def pack_conv_weight(w_oihw: torch.Tensor) -> torch.Tensor:
     """diffusers conv weight [Cout, Cin, kh, kw] -> [Cout, kh*kw*Cin] (K = (tap, cin)); pure layout."""
     co, ci, kh, kw = w_oihw.shape
     return w_oihw.permute(0, 2, 3, 1).reshape(co, kh * kw * ci).contiguous()
+
+
+def pack_conv_weight_phase(w_oihw: torch.Tensor) -> torch.Tensor:
+    """3x3 conv weight [..., Cout, Cin, 3, 3] -> the phase image [..., 4, Cout, 4 * Cin] of the nearest-2x upsample + conv (``conv2d(upsample=2)``).
+
+    Output pixel (2y + py, 2x + px) of the upsampled convolution reads the source rows y - 1 + py + a, a = 0, 1: for py = 0 row y - 1 with
+    w[0] and row y with w[1] + w[2]; for py = 1 row y with w[0] + w[1] and row y + 1 with w[2] — the same along x.  Phase 2 py + px is the 2x2
+    convolution with tap origin (py - 1, px - 1) whose taps (a, c), row-major, are those sums of 1, 2, 2 or 4 original taps; K = (tap, cin).
+    Summed in fp32 (float64 for a float64 weight), rounded to the storage type once.  Any device; leading dimensions (weight slots) pass through."""
+    assert w_oihw.dim() >= 4 and tuple(w_oihw.shape[-2:]) == (3, 3)
+    lead, (co, ci) = tuple(w_oihw.shape[:-4]), w_oihw.shape[-4:-2]
+    wf = w_oihw if w_oihw.dtype == torch.float64 else w_oihw.float()
+    rows = ((wf[..., 0, :], wf[..., 1, :] + wf[..., 2, :]), (wf[..., 0, :] + wf[..., 1, :], wf[..., 2, :]))      # [py][a]: [..., Cout, Cin, 3]
+    phases = []
+    for py in range(2):
+        for px in range(2):
+            taps = []
+            for a in range(2):
+                r = rows[py][a]
+                taps += [r[..., 0], r[..., 1] + r[..., 2]] if px == 0 else [r[..., 0] + r[..., 1], r[..., 2]]
+            phases.append(torch.stack(taps, dim=-2))                 # [..., Cout, 4 taps, Cin]
+    return torch.stack(phases, dim=-4).reshape(*lead, 4, co, 4 * ci).to(w_oihw.dtype).contiguous()
 
 
 def pack_conv_weight_wino(w_oihw: torch.Tensor) -> torch.Tensor:

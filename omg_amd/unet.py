@@ -172,9 +172,10 @@ class Upsample2D(nn.Module):
     def __init__(self, c, dtype, device):
         super().__init__()
         self.conv = Conv2d(c, c, 3, dtype=dtype, device=device)
+        self.conv.upsamples = True
 
     def forward(self, x):
-        return self.conv(x, upsample=True)      # nearest-2x folded into the conv's operand loader
+        return self.conv(x, upsample=True)      # nearest-2x folded into the conv: four 2x2 phase convolutions on the source image
 
 
 class _DownBlock(nn.Module):
