@@ -795,17 +795,29 @@ def conv3x3_nhwc_act(x: torch.Tensor, w: torch.Tensor, *, stride: int = 1, bias:
 
 
 def dwconv3x3_act(x: torch.Tensor, taps: torch.Tensor, B: int, H: int, W: int, *, stride: int = 1, bias: Optional[torch.Tensor] = None,
-                  gelu: bool = False, gelu_in: bool = False) -> torch.Tensor:
+                  gelu: bool = False, gelu_in: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Depthwise 3x3 convolution (padding 1, stride 1 | 2) of NHWC rows ``x`` [B*H*W, C]; ``taps`` [9, C] tap-major.  ``gelu`` acts on
-    the output, ``gelu_in`` on the input as it is read.  -> [B*Hout*Wout, C].  omg_dwconv3x3_act."""
+    the output, ``gelu_in`` on the input as it is read.  -> [B*Hout*Wout, C]; ``out``, if given, is that many rows of any stride >= C
+    that is a multiple of 8 (a column slice of a wider buffer), not overlapping ``x``.  omg_dwconv3x3_act."""
     _dev(x)
     M, Cc = x.shape
     assert M == B * H * W and x.stride(1) == 1 and taps.shape == (9, Cc) and taps.is_contiguous()
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-    y = torch.empty((B * Ho * Wo, Cc), dtype=x.dtype, device=x.device)
+    if out is None:
+        y = torch.empty((B * Ho * Wo, Cc), dtype=x.dtype, device=x.device)
+    else:
+        y = out
+        assert y.dim() == 2 and y.shape == (B * Ho * Wo, Cc) and y.dtype == x.dtype and y.device == x.device
+        assert y.stride(1) == 1 and (y.shape[0] <= 1 or (y.stride(0) >= Cc and y.stride(0) % 8 == 0)), "dwconv3x3_act: out row stride"
+        es, x0, y0, My = x.element_size(), x.data_ptr(), y.data_ptr(), y.shape[0]
+        if M and My and x0 < y0 + ((My - 1) * y.stride(0) + Cc) * es and y0 < x0 + ((M - 1) * x.stride(0) + Cc) * es:
+            # the same buffer: rows of the same stride, and columns that x does not have
+            dcol = abs(y0 - x0) // es % max(x.stride(0), 1)
+            assert x.stride(0) == y.stride(0) and Cc <= dcol <= x.stride(0) - Cc, "dwconv3x3_act: out overlaps x"
     t0 = _PROF.begin() if _PROF is not None else None
     L.check(L.lib().omg_dwconv3x3_act(_dt(x), x.data_ptr(), x.stride(0), B, H, W, Cc, stride, taps.data_ptr(), _p(bias),
-                                      int(gelu) | (int(gelu_in) << 1), y.data_ptr(), y.stride(0), _stream()), "omg_dwconv3x3_act")
+                                      int(gelu) | (int(gelu_in) << 1), y.data_ptr(), y.stride(0) if y.shape[0] > 1 else Cc, _stream()),
+            "omg_dwconv3x3_act")
     if _PROF is not None:
         _PROF.end("dwconv3x3", 2.0 * B * Ho * Wo * Cc * 9, t0, ("dwconv3x3", B * Ho * Wo, Cc, stride))
     return y

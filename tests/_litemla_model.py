@@ -71,8 +71,8 @@ def ulp16(t, dtype):
     return torch.exp2(e - bits)
 
 
-def held(tag, dtype, out, truth, ref32, log=None):
-    """Applies the rule to one case; what it measured goes to `log` (a list) before it asserts.  Figures: E32; the excess of the error
+def held(tag, dtype, out, truth, ref32, log=None, allow=None):
+    """Applies the rule to one case (`allow`, if given, is a further elementwise term of the bound: tests/_conv3x3_model.py); what it measured goes to `log` (a list) before it asserts.  Figures: E32; the excess of the error
     over the half ulp, over E32 (a lower bound of the kernel's fp32 error over E32, which a 16-bit output does not show directly); the
     error over the rule's bound; the share of elements that are not round16(truth)."""
     out = out.detach().cpu()
@@ -82,7 +82,7 @@ def held(tag, dtype, out, truth, ref32, log=None):
     E32 = max(float((ref32 - truth).abs().max()) if truth.numel() else 0.0, 2.0 ** -23 * tmax)
     err = (o - truth).abs()
     half = ulp16(truth, dtype) / 2
-    bound = half + C_RULE * E32
+    bound = half + C_RULE * E32 if allow is None else half + C_RULE * E32 + allow
     excess = (err - half).clamp_min(0)
     rec = dict(tag=tag, dtype=name(dtype), E32=E32, max_truth=tmax, finite=finite,
                excess_over_E32=(float(torch.nan_to_num(excess, nan=float("inf")).max()) / E32 if E32 > 0 else 0.0) if truth.numel() else 0.0,
@@ -96,7 +96,8 @@ def held(tag, dtype, out, truth, ref32, log=None):
         i = int(torch.argmax(torch.where(bad, err / bound.clamp_min(1e-300), torch.zeros_like(err))))
         r, c = divmod(i, truth.shape[1])
         raise AssertionError(f"{tag}: {int(bad.sum())} of {bad.numel()} elements break the rule; worst at row {r} column {c}: out {float(o[r, c])!r} "
-                             f"truth {float(truth[r, c])!r} error {float(err[r, c]):.3e} > ulp/2 {float(half[r, c]):.3e} + {C_RULE} * E32 {E32:.3e}")
+                             f"truth {float(truth[r, c])!r} error {float(err[r, c]):.3e} > ulp/2 {float(half[r, c]):.3e} + {C_RULE} * E32 {E32:.3e}"
+                             + ("" if allow is None else f" + allowance {float(allow[r, c]):.3e}"))
     return rec
 
 
