@@ -23,10 +23,10 @@ from __future__ import annotations
 from typing import Dict, Optional
 
 import torch
-import torch.nn as nn
 
 from . import _lib as L
 from . import ops
+from ._checkpoint import FlatWeights
 
 __all__ = ["BertTextEncoder", "check_config", "T_SKINNY"]
 
@@ -68,21 +68,24 @@ def check_config(config) -> dict:
                 types=int(cfg.get("type_vocab_size", 2)), eps=float(cfg.get("layer_norm_eps", 1e-12)))
 
 
-class BertTextEncoder(nn.Module):
-    """``BertTextEncoder(config, dtype, device, linear="auto")``; ``config``: the library's ``BertConfig`` or its dict."""
+class BertTextEncoder(FlatWeights):
+    """``BertTextEncoder(config, dtype, device, linear="auto")``; ``config``: the library's ``BertConfig`` or its dict.
+    ``load_state_dict`` takes ``sd`` under the library's names; ``prefix="model.text_backbone."`` takes this module's keys out of a
+    ``GroundingDinoForObjectDetection`` state dict and ignores the others.  ``pooler.*`` and ``embeddings.position_ids`` are dropped.
+    ``from_pretrained`` takes a checkpoint directory of a ``GroundingDinoForObjectDetection`` (the config's ``text_config``, the keys under
+    ``prefix``) or of a plain BERT (the top level of the config; pass the file's own prefix, ``""`` or ``"bert."``); ``linear`` and
+    ``t_skinny`` go to the constructor."""
+
+    check_config = staticmethod(check_config)
+    prefix = "model.text_backbone."
+    no_training = "'hidden_dropout_prob', 'attention_probs_dropout_prob'"
+    constructor_keywords = ("linear", "t_skinny")
 
     def __init__(self, config, dtype=torch.float16, device=None, linear: str = "auto", t_skinny: int = T_SKINNY):
-        super().__init__()
-        if dtype not in (torch.float16, torch.bfloat16):
-            raise L.OmgHipError(f"BertTextEncoder: dtype {dtype}; the kernels store float16 or bfloat16")
+        super().__init__(config, dtype, device)
         if linear not in ("auto", "skinny", "gemm"):
             raise L.OmgHipError(f"BertTextEncoder: linear='{linear}'; 'auto', 'skinny' or 'gemm'")
-        self.cfg = check_config(config)
         self.linear, self.t_skinny = linear, int(t_skinny)
-        self._dtype, self._device = dtype, torch.device(device) if device is not None else torch.device("cpu")
-        self._w: Dict[str, torch.Tensor] = {k: torch.zeros(s, dtype=dtype, device=self._device) for k, s in self.shapes().items()}
-        self._packed: Optional[dict] = None
-        self.eval()
 
     # ------------------------------------------------------------------ parameters
     def shapes(self) -> Dict[str, tuple]:
@@ -109,71 +112,24 @@ class BertTextEncoder(nn.Module):
             norm(p + "output.LayerNorm")
         return out
 
-    def state_dict(self, *a, **k):
-        return dict(self._w)
-
-    def load_state_dict(self, sd, strict: bool = True, prefix: str = ""):
-        """``sd`` under the library's names; ``prefix="model.text_backbone."`` takes this module's keys out of a
-        ``GroundingDinoForObjectDetection`` state dict and ignores the others.  ``pooler.*`` and ``embeddings.position_ids`` are dropped."""
-        shapes = self.shapes()
-        seen = set()
-        for k, shape in shapes.items():
-            v = sd.get(prefix + k)
-            if v is None:
-                continue
-            if tuple(v.shape) != tuple(shape):
-                raise L.OmgHipError(f"BertTextEncoder.load_state_dict: {k} is {tuple(v.shape)}, the config needs {tuple(shape)}")
-            self._w[k] = v.detach().to(device=self._device, dtype=self._dtype).contiguous().clone()
-            seen.add(k)
-        missing = [k for k in shapes if k not in seen]
-        dropped = ("pooler.", "embeddings.position_ids")
-        unexpected = [k for k in sd if k.startswith(prefix) and k[len(prefix):] not in shapes and not k[len(prefix):].startswith(dropped)]
-        if strict and (missing or unexpected):
-            raise L.OmgHipError(f"BertTextEncoder.load_state_dict: missing {missing[:6]}{' ...' if len(missing) > 6 else ''}, "
-                                f"unexpected {unexpected[:6]}{' ...' if len(unexpected) > 6 else ''}")
-        self._packed = None
-        return missing, unexpected
+    @staticmethod
+    def canonical_key(k: str, prefix: str = "") -> Optional[str]:
+        k = FlatWeights.canonical_key(k, prefix)
+        return None if k is None or k.startswith(("pooler.", "embeddings.position_ids")) else k
 
     @classmethod
-    def from_pretrained(cls, path, torch_dtype=torch.float16, device=None, prefix: str = "model.text_backbone.", linear: str = "auto",
-                        t_skinny: int = T_SKINNY, **_ignored):
-        """A local checkpoint directory (``config.json`` and ``model.safetensors`` or ``pytorch_model.bin``) of a
-        ``GroundingDinoForObjectDetection`` (the config's ``text_config``, the keys under ``prefix``) or of a plain BERT (the top level of
-        the config; pass the file's own prefix, ``""`` or ``"bert."``).  ``linear`` and ``t_skinny`` go to the constructor; other keywords (the
-        library's ``from_pretrained`` takes many) are ignored, as by the neighbouring modules."""
-        from .gdino_decoder import _read_checkpoint
-        config, sd = _read_checkpoint(path, "BertTextEncoder")
-        model = cls(config.get("text_config") or config, dtype=torch_dtype, device=device, linear=linear, t_skinny=t_skinny)
-        model.load_state_dict(sd, strict=True, prefix=prefix)
-        return model
-
-    def train(self, mode: bool = True):
-        if mode:
-            raise L.OmgHipError("BertTextEncoder: training ('hidden_dropout_prob', 'attention_probs_dropout_prob') is not built; "
-                                "the module is inference only")
-        return super().train(False)
-
-    def _apply(self, fn, *a, **k):
-        self._w = {key: fn(t) for key, t in self._w.items()}
-        any_t = next(iter(self._w.values()))
-        self._dtype, self._device, self._packed = any_t.dtype, any_t.device, None
-        return super()._apply(fn, *a, **k)
-
-    @property
-    def dtype(self):
-        return self._dtype
+    def from_state_dict(cls, config, sd, **keywords):
+        return super().from_state_dict(config.get("text_config") or config, sd, **keywords)
 
     # ------------------------------------------------------------------ kernel operands that are not the checkpoint's own tensors, built once
-    def _pk(self) -> dict:
-        if self._packed is None:
-            w = self._w
-            pk = {}
-            for i in range(self.cfg["layers"]):
-                p = f"encoder.layer.{i}.attention.self."
-                for s in ("weight", "bias"):
-                    pk[p + "qkv." + s] = torch.cat([w[p + n + "." + s] for n in ("query", "key", "value")], dim=0).contiguous()
-            self._packed = pk
-        return self._packed
+    def _pack(self) -> dict:
+        w = self._w
+        pk = {}
+        for i in range(self.cfg["layers"]):
+            p = f"encoder.layer.{i}.attention.self."
+            for s in ("weight", "bias"):
+                pk[p + "qkv." + s] = torch.cat([w[p + n + "." + s] for n in ("query", "key", "value")], dim=0).contiguous()
+        return pk
 
     # ------------------------------------------------------------------ forward
     def uses_skinny(self, T: int) -> bool:

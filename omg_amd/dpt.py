@@ -39,6 +39,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ops
+from ._checkpoint import Weight as _W, param as _param, read_checkpoint
 
 __all__ = ["DPTForDepthEstimation", "DPTImageProcessor", "DPTFeatureExtractor", "depth_condition", "check_config", "fold_weight_standardization"]
 
@@ -129,20 +130,6 @@ def check_config(cfg: dict) -> dict:
 
 
 # ------------------------------------------------------------------------------------------------ the checkpoint's module tree
-def _param(shape, dtype, device):
-    return nn.Parameter(torch.zeros(shape, dtype=dtype, device=device), requires_grad=False)
-
-
-class _W(nn.Module):
-    """Holder of ``weight`` (+ ``bias``)."""
-
-    def __init__(self, shape, bias, dtype, device):
-        super().__init__()
-        self.weight = _param(shape, dtype, device)
-        if bias:
-            self.bias = _param((bias,), dtype, device)
-
-
 class _Holder(nn.Module):
     def __init__(self, **mods):
         super().__init__()
@@ -217,20 +204,7 @@ class DPTForDepthEstimation(nn.Module):
     @classmethod
     def from_pretrained(cls, path, torch_dtype=torch.float16, device=None, **_ignored):
         """A local checkpoint directory: ``config.json`` and ``model.safetensors`` or ``pytorch_model.bin``."""
-        path = os.fspath(path)
-        cfg_file = os.path.join(path, "config.json")
-        if not os.path.isdir(path) or not os.path.exists(cfg_file):
-            raise L.OmgHipError(f"DPTForDepthEstimation.from_pretrained: {path} is not a local checkpoint directory with a config.json (nothing is downloaded)")
-        with open(cfg_file) as f:
-            config = json.load(f)
-        st, pt = os.path.join(path, "model.safetensors"), os.path.join(path, "pytorch_model.bin")
-        if os.path.exists(st):
-            from safetensors.torch import load_file
-            sd = load_file(st, device="cpu")
-        elif os.path.exists(pt):
-            sd = torch.load(pt, map_location="cpu", weights_only=True)
-        else:
-            raise L.OmgHipError(f"DPTForDepthEstimation.from_pretrained: neither model.safetensors nor pytorch_model.bin in {path}")
+        config, sd = read_checkpoint(path, "DPTForDepthEstimation")
         model = cls(config, dtype=torch_dtype, device=device)
         model.load_state_dict(sd, strict=True)
         return model.eval()

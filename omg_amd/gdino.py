@@ -28,17 +28,15 @@ Inference only: dropout and drop-path are the identity whatever the config says,
 """
 from __future__ import annotations
 
-import json
 import math
-import os
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
-import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib as L
 from . import ops
+from ._checkpoint import FlatWeights
 
 __all__ = ["GroundingDinoEncoder", "GroundingDinoEncoderOutput", "check_config"]
 
@@ -156,18 +154,15 @@ def _device_ints(rows, device) -> torch.Tensor:
     return t
 
 
-class GroundingDinoEncoder(nn.Module):
-    """``GroundingDinoEncoder(config, dtype, device)``; ``config``: the library's ``GroundingDinoConfig`` or its dict."""
+class GroundingDinoEncoder(FlatWeights):
+    """``GroundingDinoEncoder(config, dtype, device)``; ``config``: the library's ``GroundingDinoConfig`` or its dict.
+    ``load_state_dict`` takes ``sd`` under the library's names; ``prefix="model."`` takes the neck and the encoder out of a
+    ``GroundingDinoForObjectDetection`` state dict.  Keys outside the prefix, and the detector's other parts (backbone, text backbone,
+    decoder, heads), are ignored; an ``input_proj_vision`` / ``encoder.`` key this config does not have is unexpected."""
 
-    def __init__(self, config, dtype=torch.float16, device=None):
-        super().__init__()
-        if dtype not in (torch.float16, torch.bfloat16):
-            raise L.OmgHipError(f"GroundingDinoEncoder: dtype {dtype}; the kernels store float16 or bfloat16")
-        self.cfg = check_config(config)
-        self._dtype, self._device = dtype, torch.device(device) if device is not None else torch.device("cpu")
-        self._w: Dict[str, torch.Tensor] = {k: torch.zeros(s, dtype=dtype, device=self._device) for k, s in self.shapes().items()}
-        self._packed: Optional[dict] = None
-        self.eval()
+    check_config = staticmethod(check_config)
+    prefix = "model."
+    no_training = ", ".join(repr(k) for k in _DROPS)
 
     # ------------------------------------------------------------------ parameters
     def shapes(self) -> Dict[str, tuple]:
@@ -207,96 +202,31 @@ class GroundingDinoEncoder(nn.Module):
                 out[m + n + ".weight"], out[m + n + ".bias"] = (d,), (d,)
         return out
 
-    def state_dict(self, *a, **k):
-        return dict(self._w)
-
-    def load_state_dict(self, sd, strict: bool = True, prefix: str = ""):
-        """``sd`` under the library's names; ``prefix="model."`` takes the neck and the encoder out of a
-        ``GroundingDinoForObjectDetection`` state dict.  Keys outside the prefix, and the detector's other parts (backbone, text
-        backbone, decoder, heads), are ignored; an ``input_proj_vision`` / ``encoder.`` key this config does not have is unexpected."""
-        shapes = self.shapes()
-        seen, unexpected = set(), []
-        for k, v in sd.items():
-            if prefix:
-                if not k.startswith(prefix):
-                    continue
-                k = k[len(prefix):]
-            if k not in shapes:
-                if k.startswith(("input_proj_vision.", "encoder.layers.", "level_embed", "text_projection.")):
-                    unexpected.append(k)
-                continue
-            if tuple(v.shape) != tuple(shapes[k]):
-                raise L.OmgHipError(f"GroundingDinoEncoder.load_state_dict: {k} is {tuple(v.shape)}, the config needs {tuple(shapes[k])}")
-            self._w[k] = v.detach().to(device=self._device, dtype=self._dtype).contiguous().clone()
-            seen.add(k)
-        missing = [k for k in shapes if k not in seen]
-        if strict and (missing or unexpected):
-            raise L.OmgHipError(f"GroundingDinoEncoder.load_state_dict: missing {missing[:6]}{' ...' if len(missing) > 6 else ''}, "
-                                f"unexpected {unexpected[:6]}{' ...' if len(unexpected) > 6 else ''}")
-        self._packed = None
-        return missing, unexpected
-
-    @classmethod
-    def from_pretrained(cls, path, torch_dtype=torch.float16, device=None, prefix: str = "model.", **_ignored):
-        """A local checkpoint directory of a ``GroundingDinoForObjectDetection``: ``config.json`` and ``model.safetensors`` or
-        ``pytorch_model.bin``."""
-        path = os.fspath(path)
-        cfg_file = os.path.join(path, "config.json")
-        if not os.path.isdir(path) or not os.path.exists(cfg_file):
-            raise L.OmgHipError(f"GroundingDinoEncoder.from_pretrained: {path} is not a local checkpoint directory with a config.json (nothing is downloaded)")
-        with open(cfg_file) as f:
-            config = json.load(f)
-        st, pt = os.path.join(path, "model.safetensors"), os.path.join(path, "pytorch_model.bin")
-        if os.path.exists(st):
-            from safetensors.torch import load_file
-            sd = load_file(st, device="cpu")
-        elif os.path.exists(pt):
-            sd = torch.load(pt, map_location="cpu", weights_only=True)
-        else:
-            raise L.OmgHipError(f"GroundingDinoEncoder.from_pretrained: neither model.safetensors nor pytorch_model.bin in {path}")
-        model = cls(config, dtype=torch_dtype, device=device)
-        model.load_state_dict(sd, strict=True, prefix=prefix)
-        return model
-
-    def train(self, mode: bool = True):
-        if mode:
-            raise L.OmgHipError(f"GroundingDinoEncoder: training ({', '.join(repr(k) for k in _DROPS)}) is not built; the module is inference only")
-        return super().train(False)
-
-    def _apply(self, fn, *a, **k):
-        self._w = {key: fn(t) for key, t in self._w.items()}
-        any_t = next(iter(self._w.values()))
-        self._dtype, self._device, self._packed = any_t.dtype, any_t.device, None
-        return super()._apply(fn, *a, **k)
-
-    @property
-    def dtype(self):
-        return self._dtype
+    def _unexpected(self, k, ck):
+        return ck if ck.startswith(("input_proj_vision.", "encoder.layers.", "level_embed", "text_projection.")) else None
 
     # ------------------------------------------------------------------ kernel operands that are not the checkpoint's own tensors, built once
-    def _pk(self) -> dict:
-        if self._packed is None:
-            w, c = self._w, self.cfg
-            cat = lambda names: torch.cat([w[n] for n in names], dim=0).contiguous()
-            pk = {}
-            for l in range(c["levels"]):
-                k = f"input_proj_vision.{l}.0.weight"
-                # 1x1: the GEMM weight [256, C]; 3x3: [Cout, 3, 3, Cin] for the NHWC convolution
-                pk[k] = w[k].reshape(w[k].shape[0], -1).contiguous() if l < len(c["in_channels"]) else w[k].permute(0, 2, 3, 1).contiguous()
-            for i in range(c["layers"]):
-                p = f"encoder.layers.{i}."
-                f, t, m = p + "fusion_layer.attn.", p + "text_enhancer_layer.self_attn.", p + "deformable_layer.self_attn."
-                pk[f + "vis.weight"], pk[f + "vis.bias"] = cat([f + "vision_proj.weight", f + "values_vision_proj.weight"]), cat([f + "vision_proj.bias", f + "values_vision_proj.bias"])
-                pk[f + "txt.weight"], pk[f + "txt.bias"] = cat([f + "text_proj.weight", f + "values_text_proj.weight"]), cat([f + "text_proj.bias", f + "values_text_proj.bias"])
-                for side in ("vision", "text"):
-                    g = w[p + f"fusion_layer.{side}_param"].float()
-                    pk[f + f"out_{side}.weight"] = (g[:, None] * w[f + f"out_{side}_proj.weight"].float()).to(self._dtype).contiguous()
-                    pk[f + f"out_{side}.bias"] = (g * w[f + f"out_{side}_proj.bias"].float()).to(self._dtype).contiguous()
-                pk[t + "qk.weight"], pk[t + "qk.bias"] = cat([t + "query.weight", t + "key.weight"]), cat([t + "query.bias", t + "key.bias"])
-                pk[m + "ow.weight"] = cat([m + "sampling_offsets.weight", m + "attention_weights.weight"])
-                pk[m + "ow.bias"] = cat([m + "sampling_offsets.bias", m + "attention_weights.bias"])
-            self._packed = pk
-        return self._packed
+    def _pack(self) -> dict:
+        w, c = self._w, self.cfg
+        cat = lambda names: torch.cat([w[n] for n in names], dim=0).contiguous()
+        pk = {}
+        for l in range(c["levels"]):
+            k = f"input_proj_vision.{l}.0.weight"
+            # 1x1: the GEMM weight [256, C]; 3x3: [Cout, 3, 3, Cin] for the NHWC convolution
+            pk[k] = w[k].reshape(w[k].shape[0], -1).contiguous() if l < len(c["in_channels"]) else w[k].permute(0, 2, 3, 1).contiguous()
+        for i in range(c["layers"]):
+            p = f"encoder.layers.{i}."
+            f, t, m = p + "fusion_layer.attn.", p + "text_enhancer_layer.self_attn.", p + "deformable_layer.self_attn."
+            pk[f + "vis.weight"], pk[f + "vis.bias"] = cat([f + "vision_proj.weight", f + "values_vision_proj.weight"]), cat([f + "vision_proj.bias", f + "values_vision_proj.bias"])
+            pk[f + "txt.weight"], pk[f + "txt.bias"] = cat([f + "text_proj.weight", f + "values_text_proj.weight"]), cat([f + "text_proj.bias", f + "values_text_proj.bias"])
+            for side in ("vision", "text"):
+                g = w[p + f"fusion_layer.{side}_param"].float()
+                pk[f + f"out_{side}.weight"] = (g[:, None] * w[f + f"out_{side}_proj.weight"].float()).to(self._dtype).contiguous()
+                pk[f + f"out_{side}.bias"] = (g * w[f + f"out_{side}_proj.bias"].float()).to(self._dtype).contiguous()
+            pk[t + "qk.weight"], pk[t + "qk.bias"] = cat([t + "query.weight", t + "key.weight"]), cat([t + "query.bias", t + "key.bias"])
+            pk[m + "ow.weight"] = cat([m + "sampling_offsets.weight", m + "attention_weights.weight"])
+            pk[m + "ow.bias"] = cat([m + "sampling_offsets.bias", m + "attention_weights.bias"])
+        return pk
 
     # ------------------------------------------------------------------ forward
     def _nhwc(self, fm: torch.Tensor) -> torch.Tensor:

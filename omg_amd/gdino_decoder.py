@@ -26,8 +26,6 @@ Inference only; ``output_attentions`` and the loss are not built.  There is no C
 """
 from __future__ import annotations
 
-import json
-import os
 from typing import Dict, List, Optional, Sequence
 
 import torch
@@ -35,6 +33,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ops
+from ._checkpoint import FlatWeights, read_checkpoint
 
 __all__ = ["GroundingDinoDecoderHead", "GroundingDinoDetectionOutput", "GroundingDinoDetector", "check_config", "detect", "phrases",
            "text_masks_from_input_ids", "SPECIAL_TOKENS"]
@@ -127,18 +126,12 @@ def proposals(mask_flatten: torch.Tensor, spatial: Sequence[Sequence[int]]):
     return logit.contiguous(), keep
 
 
-class GroundingDinoDecoderHead(nn.Module):
+class GroundingDinoDecoderHead(FlatWeights):
     """``GroundingDinoDecoderHead(config, dtype, device)``; ``config``: the library's ``GroundingDinoConfig`` or its dict."""
 
-    def __init__(self, config, dtype=torch.float16, device=None):
-        super().__init__()
-        if dtype not in (torch.float16, torch.bfloat16):
-            raise L.OmgHipError(f"GroundingDinoDecoderHead: dtype {dtype}; the kernels store float16 or bfloat16")
-        self.cfg = check_config(config)
-        self._dtype, self._device = dtype, torch.device(device) if device is not None else torch.device("cpu")
-        self._w: Dict[str, torch.Tensor] = {k: torch.zeros(s, dtype=dtype, device=self._device) for k, s in self.shapes().items()}
-        self._packed: Optional[dict] = None
-        self.eval()
+    check_config = staticmethod(check_config)
+    prefix = "model."
+    no_training = "'dropout', 'attention_dropout', 'activation_dropout', the loss"
 
     # ------------------------------------------------------------------ parameters
     def shapes(self) -> Dict[str, tuple]:
@@ -179,79 +172,36 @@ class GroundingDinoDecoderHead(nn.Module):
             mlp(f"decoder.bbox_embed.{i}", d, None)
         return out
 
-    def state_dict(self, *a, **k):
-        return dict(self._w)
-
     def load_state_dict(self, sd, strict: bool = True, prefix: str = ""):
         """``sd`` under the library's names; ``prefix="model."`` takes this module's keys out of a ``GroundingDinoForObjectDetection``
         state dict and ignores the others.  The box heads are looked for under ``{prefix}decoder.bbox_embed.*`` and under the detection
         model's own ``bbox_embed.*``; where both are there they must be equal."""
-        shapes = self.shapes()
-        seen = set()
-        for k, shape in shapes.items():
-            cands = [prefix + k]
-            if k.startswith("decoder.bbox_embed."):
-                cands.append(k[len("decoder."):])
-            found = [sd[n] for n in cands if n in sd]
-            if not found:
-                continue
-            if len(found) == 2 and not torch.equal(found[0].detach().cpu(), found[1].detach().cpu()):
-                raise L.OmgHipError(f"GroundingDinoDecoderHead.load_state_dict: {cands[0]} and {cands[1]} differ; the library ties them")
-            v = found[0]
-            if tuple(v.shape) != tuple(shape):
-                raise L.OmgHipError(f"GroundingDinoDecoderHead.load_state_dict: {k} is {tuple(v.shape)}, the config needs {tuple(shape)}")
-            self._w[k] = v.detach().to(device=self._device, dtype=self._dtype).contiguous().clone()
-            seen.add(k)
-        missing = [k for k in shapes if k not in seen]
-        mine = ("enc_output", "encoder_output_bbox_embed.", "query_position_embeddings.", "decoder.")
-        unexpected = [k for k in sd if k.startswith(prefix) and k[len(prefix):].startswith(mine) and k[len(prefix):] not in shapes]
-        if strict and (missing or unexpected):
-            raise L.OmgHipError(f"GroundingDinoDecoderHead.load_state_dict: missing {missing[:6]}{' ...' if len(missing) > 6 else ''}, "
-                                f"unexpected {unexpected[:6]}{' ...' if len(unexpected) > 6 else ''}")
-        self._packed = None
-        return missing, unexpected
+        shapes, sd = self.shapes(), dict(sd)
+        for top in [k for k in sd if k.startswith("bbox_embed.") and "decoder." + k in shapes]:
+            mine = prefix + "decoder." + top
+            if mine not in sd:
+                sd[mine] = sd[top]
+            elif not torch.equal(sd[mine].detach().cpu(), sd[top].detach().cpu()):
+                raise L.OmgHipError(f"GroundingDinoDecoderHead.load_state_dict: {mine} and {top} differ; the library ties them")
+        return super().load_state_dict(sd, strict, prefix)
 
-    @classmethod
-    def from_pretrained(cls, path, torch_dtype=torch.float16, device=None, prefix: str = "model.", **_ignored):
-        """A local checkpoint directory of a ``GroundingDinoForObjectDetection``: ``config.json`` and ``model.safetensors`` or
-        ``pytorch_model.bin``."""
-        config, sd = _read_checkpoint(path, "GroundingDinoDecoderHead")
-        model = cls(config, dtype=torch_dtype, device=device)
-        model.load_state_dict(sd, strict=True, prefix=prefix)
-        return model
-
-    def train(self, mode: bool = True):
-        if mode:
-            raise L.OmgHipError("GroundingDinoDecoderHead: training ('dropout', 'attention_dropout', 'activation_dropout', the loss) is not built; "
-                                "the module is inference only")
-        return super().train(False)
-
-    def _apply(self, fn, *a, **k):
-        self._w = {key: fn(t) for key, t in self._w.items()}
-        any_t = next(iter(self._w.values()))
-        self._dtype, self._device, self._packed = any_t.dtype, any_t.device, None
-        return super()._apply(fn, *a, **k)
-
-    @property
-    def dtype(self):
-        return self._dtype
+    def _unexpected(self, k, ck):
+        return k if ck.startswith(("enc_output", "encoder_output_bbox_embed.", "query_position_embeddings.", "decoder.")) else None
 
     # ------------------------------------------------------------------ kernel operands that are not the checkpoint's own tensors, built once
-    def _pk(self) -> dict:
-        if self._packed is None:
-            w, c = self._w, self.cfg
-            cat = lambda names: torch.cat([w[n] for n in names], dim=0).contiguous()
-            lay = [f"decoder.layers.{i}." for i in range(c["layers"])]
-            pk = {}
-            for s in ("weight", "bias"):
-                # constant over the layers: one GEMM of the image memory for every layer's value_proj, one of the text for every k | v
-                pk["value_all." + s] = cat([p + "encoder_attn.value_proj." + s for p in lay])
-                pk["text_kv_all." + s] = cat([p + f"encoder_attn_text.{n}." + s for p in lay for n in ("key", "value")])
-                for p in lay:
-                    pk[p + "self_attn.qk." + s] = cat([p + "self_attn.query." + s, p + "self_attn.key." + s])
-                    pk[p + "encoder_attn.ow." + s] = cat([p + "encoder_attn.sampling_offsets." + s, p + "encoder_attn.attention_weights." + s])
-            self._packed = pk
-        return self._packed
+    def _pack(self) -> dict:
+        w, c = self._w, self.cfg
+        cat = lambda names: torch.cat([w[n] for n in names], dim=0).contiguous()
+        lay = [f"decoder.layers.{i}." for i in range(c["layers"])]
+        pk = {}
+        for s in ("weight", "bias"):
+            # constant over the layers: one GEMM of the image memory for every layer's value_proj, one of the text for every k | v
+            pk["value_all." + s] = cat([p + "encoder_attn.value_proj." + s for p in lay])
+            pk["text_kv_all." + s] = cat([p + f"encoder_attn_text.{n}." + s for p in lay for n in ("key", "value")])
+            for p in lay:
+                pk[p + "self_attn.qk." + s] = cat([p + "self_attn.query." + s, p + "self_attn.key." + s])
+                pk[p + "encoder_attn.ow." + s] = cat([p + "encoder_attn.sampling_offsets." + s, p + "encoder_attn.attention_weights." + s])
+        return pk
 
     # ------------------------------------------------------------------ forward
     def _lin(self, x, name, residual=None, relu=False):
@@ -363,24 +313,6 @@ class GroundingDinoDecoderHead(nn.Module):
             all_pred_boxes=tuple(all_boxes) if output_hidden_states else None)
 
 
-def _read_checkpoint(path, who):
-    path = os.fspath(path)
-    cfg_file = os.path.join(path, "config.json")
-    if not os.path.isdir(path) or not os.path.exists(cfg_file):
-        raise L.OmgHipError(f"{who}.from_pretrained: {path} is not a local checkpoint directory with a config.json (nothing is downloaded)")
-    with open(cfg_file) as f:
-        config = json.load(f)
-    st, pt = os.path.join(path, "model.safetensors"), os.path.join(path, "pytorch_model.bin")
-    if os.path.exists(st):
-        from safetensors.torch import load_file
-        sd = load_file(st, device="cpu")
-    elif os.path.exists(pt):
-        sd = torch.load(pt, map_location="cpu", weights_only=True)
-    else:
-        raise L.OmgHipError(f"{who}.from_pretrained: neither model.safetensors nor pytorch_model.bin in {path}")
-    return config, sd
-
-
 # ------------------------------------------------------------------ front ends
 def detect(outputs, box_threshold: float = 0.3, text_threshold: float = 0.25):
     """What the original package's ``predict`` computes before it decodes phrases, per sample: ``scores = sigmoid(logits).max(-1)``, the
@@ -423,13 +355,13 @@ class GroundingDinoDetector(nn.Module):
         from .swin import SwinBackbone
         if text_backbone not in ("torch", "hip"):
             raise L.OmgHipError(f"GroundingDinoDetector.from_pretrained: text_backbone='{text_backbone}'; 'torch' or 'hip'")
-        config, sd = _read_checkpoint(path, "GroundingDinoDetector")
-        backbone = SwinBackbone.from_pretrained(path, torch_dtype=torch_dtype, device=device, prefix="model.backbone.conv_encoder.model.")
-        encoder = GroundingDinoEncoder.from_pretrained(path, torch_dtype=torch_dtype, device=device)
-        head = GroundingDinoDecoderHead.from_pretrained(path, torch_dtype=torch_dtype, device=device)
+        config, sd = read_checkpoint(path, "GroundingDinoDetector")          # read once: the four parts are built from this pair
+        backbone = SwinBackbone.from_state_dict(config, sd, torch_dtype=torch_dtype, device=device, prefix="model.backbone.conv_encoder.model.")
+        encoder = GroundingDinoEncoder.from_state_dict(config, sd, torch_dtype=torch_dtype, device=device)
+        head = GroundingDinoDecoderHead.from_state_dict(config, sd, torch_dtype=torch_dtype, device=device)
         if text_backbone == "hip":
             from .bert import BertTextEncoder
-            return cls(backbone, BertTextEncoder.from_pretrained(path, torch_dtype=torch_dtype, device=device), encoder, head)
+            return cls(backbone, BertTextEncoder.from_state_dict(config, sd, torch_dtype=torch_dtype, device=device), encoder, head)
         from transformers import AutoConfig, AutoModel
         tc = dict(config.get("text_config") or {})
         text = AutoModel.from_config(AutoConfig.for_model(tc.pop("model_type", "bert"), **tc), add_pooling_layer=False)

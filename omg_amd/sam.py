@@ -28,37 +28,12 @@ import torch.nn as nn
 from . import _lib as L
 from . import ops
 from . import efficientvit as _ev
+from ._checkpoint import Seq as _Seq, Weight as _Weight
 from .efficientvit import EfficientViTSamConfig, EfficientViTSamImageEncoder
 from .litemla import LiteMLA
 
 __all__ = ["SamPromptEncoder", "SamMaskDecoder", "EfficientViTSam", "EfficientViTSamPredictor", "efficientvit_sam", "efficientvit_sam_xl0",
            "efficientvit_sam_xl1", "create_sam_model", "set_norm_eps", "EfficientViTSamConfig", "EfficientViTSamImageEncoder"]
-
-
-def _param(shape, dtype, device):
-    return nn.Parameter(torch.zeros(shape, dtype=dtype, device=device), requires_grad=False)
-
-
-class _Weight(nn.Module):
-    """Holder of ``weight`` (+ ``bias``): an Embedding, Linear, LayerNorm or convolution of the checkpoint."""
-
-    def __init__(self, shape, bias, dtype, device):
-        super().__init__()
-        self.weight = _param(shape, dtype, device)
-        if bias:
-            self.bias = _param((bias,), dtype, device)
-
-
-class _Seq(nn.Module):
-    """Children under the indices of an nn.Sequential whose activations hold no weights."""
-
-    def __init__(self, mods: Dict[int, nn.Module]):
-        super().__init__()
-        for i, m in mods.items():
-            self.add_module(str(i), m)
-
-    def __getitem__(self, i):
-        return getattr(self, str(i))
 
 
 # ---------------------------------------------------------------------------------------------- prompt encoder

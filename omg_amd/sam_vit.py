@@ -29,22 +29,9 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ops
+from ._checkpoint import Seq as _Seq, Weight as _Weight, param as _param
 
 __all__ = ["SamImageEncoderViT"]
-
-
-def _param(shape, dtype, device):
-    return nn.Parameter(torch.zeros(shape, dtype=dtype, device=device), requires_grad=False)
-
-
-class _Weight(nn.Module):
-    """Holder of ``weight`` (+ ``bias``): a Linear, LayerNorm or convolution of the checkpoint."""
-
-    def __init__(self, shape, bias, dtype, device):
-        super().__init__()
-        self.weight = _param(shape, dtype, device)
-        if bias:
-            self.bias = _param((bias,), dtype, device)
 
 
 class _PatchEmbed(nn.Module):
@@ -81,16 +68,6 @@ class _Block(nn.Module):
         self.attn = _Attention(dim, heads, (window, window) if window else (grid, grid), dtype, device)
         self.norm2 = _Weight((dim,), dim, dtype, device)
         self.mlp = _MLP(dim, int(dim * mlp_ratio), dtype, device)
-
-
-class _Seq(nn.Module):
-    def __init__(self, mods):
-        super().__init__()
-        for i, m in enumerate(mods):
-            self.add_module(str(i), m)
-
-    def __getitem__(self, i):
-        return getattr(self, str(i))
 
 
 class SamImageEncoderViT(nn.Module):

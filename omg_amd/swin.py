@@ -22,15 +22,13 @@ is not built.  Inference only.  There is no CPU path: ``forward`` on a CPU tenso
 """
 from __future__ import annotations
 
-import json
-import os
 from typing import Dict, List, Optional, Tuple
 
 import torch
-import torch.nn as nn
 
 from . import _lib as L
 from . import ops
+from ._checkpoint import FlatWeights
 
 __all__ = ["SwinBackbone", "SwinBackboneOutput", "swin_from_groundingdino", "check_config"]
 
@@ -144,20 +142,18 @@ class SwinBackboneOutput:
         self.attentions = None
 
 
-class SwinBackbone(nn.Module):
-    """``SwinBackbone(config, dtype, device)``; ``config``: the library's ``SwinConfig``, its dict, or a ``GroundingDinoConfig``."""
+class SwinBackbone(FlatWeights):
+    """``SwinBackbone(config, dtype, device)``; ``config``: the library's ``SwinConfig``, its dict, or a ``GroundingDinoConfig``.
+    ``load_state_dict`` takes ``sd`` under the library's names or the Hub checkpoints' names; ``prefix="model.backbone.conv_encoder.model."``
+    takes the backbone out of a ``GroundingDinoForObjectDetection`` state dict (its other keys are ignored)."""
+
+    check_config = staticmethod(check_config)
+    no_training = "dropout, 'drop_path_rate'"
 
     def __init__(self, config, dtype=torch.float16, device=None):
-        super().__init__()
-        if dtype not in (torch.float16, torch.bfloat16):
-            raise L.OmgHipError(f"SwinBackbone: dtype {dtype}; the kernels store float16 or bfloat16")
-        self.cfg = check_config(config)
-        self._dtype, self._device = dtype, torch.device(device) if device is not None else torch.device("cpu")
-        self._w: Dict[str, torch.Tensor] = {k: torch.zeros(s, dtype=dtype, device=self._device) for k, s in self.shapes().items()}
-        self._packed: Optional[dict] = None
+        super().__init__(config, dtype, device)
         self.out_features = list(self.cfg["out_features"])
         self.channels = [self.cfg["embed_dim"] << (int(s[5:]) - 1) for s in self.out_features]
-        self.eval()
 
     # ------------------------------------------------------------------ parameters
     def shapes(self) -> Dict[str, tuple]:
@@ -186,100 +182,35 @@ class SwinBackbone(nn.Module):
             out[f"hidden_states_norms.{st}.weight"], out[f"hidden_states_norms.{st}.bias"] = (C,), (C,)
         return out
 
-    def state_dict(self, *a, **k):
-        return dict(self._w)
-
     @staticmethod
     def canonical_key(k: str, prefix: str = "") -> Optional[str]:
         """A checkpoint key -> this module's key; None for what is ignored (a stored relative_position_index, SwinModel's final
         layernorm, keys outside ``prefix``)."""
-        if prefix:
-            if not k.startswith(prefix):
-                return None
-            k = k[len(prefix):]
-        if k.endswith("relative_position_index") or k.startswith("swin.layernorm."):
+        k = FlatWeights.canonical_key(k, prefix)
+        if k is None or k.endswith("relative_position_index") or k.startswith("swin.layernorm."):
             return None
         for a, b in _HUB_NAMES:
             if a in k:
                 return k.replace(a, b)
         return k
 
-    def load_state_dict(self, sd, strict: bool = True, prefix: str = ""):
-        """``sd`` under the library's names or the Hub checkpoints' names; ``prefix="model.backbone.conv_encoder.model."`` takes the
-        backbone out of a ``GroundingDinoForObjectDetection`` state dict (its other keys are ignored)."""
-        shapes = self.shapes()
-        seen, unexpected = set(), []
-        for k, v in sd.items():
-            ck = self.canonical_key(k, prefix)
-            if ck is None:
-                continue
-            if ck not in shapes:
-                unexpected.append(k)
-                continue
-            if tuple(v.shape) != tuple(shapes[ck]):
-                why = " (interpolating a relative-position table is not built: 'window_size')" if ck.endswith("relative_position_bias_table") else ""
-                raise L.OmgHipError(f"SwinBackbone.load_state_dict: {k} is {tuple(v.shape)}, the config needs {tuple(shapes[ck])}{why}")
-            self._w[ck] = v.detach().to(device=self._device, dtype=self._dtype).contiguous().clone()
-            seen.add(ck)
-        missing = [k for k in shapes if k not in seen]
-        if strict and (missing or unexpected):
-            raise L.OmgHipError(f"SwinBackbone.load_state_dict: missing {missing[:6]}{' ...' if len(missing) > 6 else ''}, "
-                                f"unexpected {unexpected[:6]}{' ...' if len(unexpected) > 6 else ''}")
-        self._packed = None
-        return missing, unexpected
-
-    @classmethod
-    def from_pretrained(cls, path, torch_dtype=torch.float16, device=None, prefix: str = "", **_ignored):
-        """A local checkpoint directory: ``config.json`` and ``model.safetensors`` or ``pytorch_model.bin``."""
-        path = os.fspath(path)
-        cfg_file = os.path.join(path, "config.json")
-        if not os.path.isdir(path) or not os.path.exists(cfg_file):
-            raise L.OmgHipError(f"SwinBackbone.from_pretrained: {path} is not a local checkpoint directory with a config.json (nothing is downloaded)")
-        with open(cfg_file) as f:
-            config = json.load(f)
-        st, pt = os.path.join(path, "model.safetensors"), os.path.join(path, "pytorch_model.bin")
-        if os.path.exists(st):
-            from safetensors.torch import load_file
-            sd = load_file(st, device="cpu")
-        elif os.path.exists(pt):
-            sd = torch.load(pt, map_location="cpu", weights_only=True)
-        else:
-            raise L.OmgHipError(f"SwinBackbone.from_pretrained: neither model.safetensors nor pytorch_model.bin in {path}")
-        model = cls(config, dtype=torch_dtype, device=device)
-        model.load_state_dict(sd, strict=True, prefix=prefix)
-        return model
-
-    def train(self, mode: bool = True):
-        if mode:
-            raise L.OmgHipError("SwinBackbone: training (dropout, 'drop_path_rate') is not built; the module is inference only")
-        return super().train(False)
-
-    def _apply(self, fn, *a, **k):
-        self._w = {key: fn(t) for key, t in self._w.items()}
-        any_t = next(iter(self._w.values()))
-        self._dtype, self._device, self._packed = any_t.dtype, any_t.device, None
-        return super()._apply(fn, *a, **k)
-
-    @property
-    def dtype(self):
-        return self._dtype
+    def _misshapen(self, k, ck):
+        return k, " (interpolating a relative-position table is not built: 'window_size')" if ck.endswith("relative_position_bias_table") else ""
 
     # ------------------------------------------------------------------ kernel operands that are not the checkpoint's own tensors, built once
-    def _pk(self) -> dict:
-        if self._packed is None:
-            w, E = self._w, self.cfg["embed_dim"]
-            pk = {}
-            pw = torch.zeros((E, PATCH_K), dtype=self._dtype, device=self._device)
-            pw[:, :48] = w["swin.embeddings.patch_embeddings.projection.weight"].reshape(E, 48)
-            pk["patch"] = pw
-            for li, depth in enumerate(self.cfg["depths"]):
-                for bi in range(depth):
-                    a = f"swin.encoder.layers.{li}.blocks.{bi}.attention."
-                    pk[a + "qkv.weight"] = torch.cat([w[a + f"{n}_proj.weight"] for n in "qkv"], dim=0).contiguous()
-                    pk[a + "qkv.bias"] = torch.cat([w[a + f"{n}_proj.bias"] for n in "qkv"], dim=0).contiguous()
-                    pk[a + "pad_kv"] = pk[a + "qkv.bias"][(E << li):]                      # k | v of a padded position: the bias slices
-            self._packed = pk
-        return self._packed
+    def _pack(self) -> dict:
+        w, E = self._w, self.cfg["embed_dim"]
+        pk = {}
+        pw = torch.zeros((E, PATCH_K), dtype=self._dtype, device=self._device)
+        pw[:, :48] = w["swin.embeddings.patch_embeddings.projection.weight"].reshape(E, 48)
+        pk["patch"] = pw
+        for li, depth in enumerate(self.cfg["depths"]):
+            for bi in range(depth):
+                a = f"swin.encoder.layers.{li}.blocks.{bi}.attention."
+                pk[a + "qkv.weight"] = torch.cat([w[a + f"{n}_proj.weight"] for n in "qkv"], dim=0).contiguous()
+                pk[a + "qkv.bias"] = torch.cat([w[a + f"{n}_proj.bias"] for n in "qkv"], dim=0).contiguous()
+                pk[a + "pad_kv"] = pk[a + "qkv.bias"][(E << li):]                      # k | v of a padded position: the bias slices
+        return pk
 
     # ------------------------------------------------------------------ forward
     @torch.no_grad()
