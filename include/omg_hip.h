@@ -872,6 +872,32 @@ typedef struct {
 int omg_lora_rownorm(int dtype, int N, int K, const void* W, const omg_lora_term* term, float* norm, void* stream);
 int omg_lora_merge(const omg_lora_merge_args* a, void* stream);
 
+/* ------------------------------------------------------------------------
+ * The demos' Canny edge condition, cv2.Canny(image, threshold1, threshold2) at apertureSize 3 and L2gradient False, on the device
+ * (omg_amd/canny.py: the arithmetic as a numpy model, written from OpenCV's published algorithm).  Integers throughout; every result is a
+ * function of its input alone, whatever order the workgroups run in.
+ *
+ * omg_canny_nms: uint8 image [B][H][W][C] (C 1 or 3, contiguous, any byte alignment) -> uint8 state [B][H][W], one launch:
+ *     dx, dy  3x3 Sobel per channel on the replicated border; mag = |dx| + |dy|; with C = 3 the channel of the largest mag (the lowest on a tie);
+ *     mag counts as 0 outside the image; a pixel with mag > low is kept when it beats its two neighbours along the gradient's sector
+ *     (|dy| 2^15 < |dx| 13573: left (>) and right (>=); |dy| 2^15 > |dx| 79109: up (>) and down (>=); else the diagonal pair, both >);
+ *     state = 0 not kept, 1 kept and mag <= high, 2 kept and mag > high.
+ *   A workgroup owns 64 x 16 pixels and stages their source bytes with a two-pixel halo in LDS through aligned dword loads (nothing
+ *   outside the tensor is read: its first and last partial dwords go byte by byte); gradients and magnitudes never go to memory.
+ * omg_canny_hysteresis: state [B][H][W] -> edges: set where the state is not 0 and the pixel's 8-connected component of non-zero states
+ *   holds a state >= 2.  Union-find over pixel indices in four launches (three when the image is one tile), the same for any data; no
+ *   host synchronisation, no copy, no kernel waits for another workgroup.  workspace: omg_canny_hysteresis_ws_bytes bytes, 4-byte
+ *   aligned, written before it is read (nothing to initialise).  out_form:
+ *     0  uint8 [B][H][W]      0 / 255
+ *     1  uint8 [B][H][W][3]   the same byte three times (get_cannyedge's image)
+ *     2  [B][3][H][W] of out_dtype (OMG_F16 / OMG_BF16 / OMG_F32)   0 / 1, what a ControlNet takes (image / 255, planar)
+ * Refused with a message: NULL operands, C not 1 or 3, sizes below 1, B > 65535, H > 16 * 65535, B H W >= 2^29, low < 0 or high < low,
+ *   an unknown out_form / out_dtype, a misaligned workspace or planar output.
+ * ---------------------------------------------------------------------- */
+int omg_canny_nms(int B, int H, int W, int C, const uint8_t* image, int low, int high, uint8_t* state, void* stream);
+int64_t omg_canny_hysteresis_ws_bytes(int B, int H, int W);
+int omg_canny_hysteresis(int B, int H, int W, const uint8_t* state, void* workspace, int out_form, int out_dtype, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

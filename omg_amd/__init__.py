@@ -11,8 +11,9 @@ _SWIN = ("SwinBackbone", "swin_from_groundingdino")
 _GDINO = ("GroundingDinoEncoder", "GroundingDinoEncoderOutput")
 _GDINO_DECODER = ("GroundingDinoDecoderHead", "GroundingDinoDetectionOutput", "GroundingDinoDetector")
 _BERT = ("BertTextEncoder",)
+_CANNY = ("Canny", "canny_condition")
 _GROUNDED_SAM = ("GroundedSam", "predict", "load_image_dino", "box_cxcywh_to_xyxy", "get_size_with_aspect_ratio")
-__all__ = list(_SAM) + list(_SAM_VIT) + list(_SEGMENT_ANYTHING) + list(_DPT) + list(_SWIN) + list(_GDINO) + list(_GDINO_DECODER) + list(_BERT) + list(_GROUNDED_SAM)
+__all__ = list(_SAM) + list(_SAM_VIT) + list(_SEGMENT_ANYTHING) + list(_DPT) + list(_SWIN) + list(_GDINO) + list(_GDINO_DECODER) + list(_BERT) + list(_GROUNDED_SAM) + list(_CANNY)
 
 
 def __getattr__(name):          # the segmenter's public names, imported on first use (omg_amd.sam pulls in torch and the kernels' bindings)
@@ -43,4 +44,7 @@ def __getattr__(name):          # the segmenter's public names, imported on firs
     if name in _GROUNDED_SAM:
         from . import grounded_sam
         return getattr(grounded_sam, name)
+    if name in _CANNY:
+        from . import canny
+        return getattr(canny, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

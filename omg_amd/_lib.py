@@ -240,6 +240,9 @@ SYMBOLS = {
     "omg_image_resize_v": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp]),
     "omg_lora_rownorm": (c_i32, [c_i32, c_i32, c_i32, c_vp, C.POINTER(LoraTermDesc), c_vp, c_vp]),
     "omg_lora_merge": (c_i32, [C.POINTER(LoraMergeArgs), c_vp]),
+    "omg_canny_nms": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp]),
+    "omg_canny_hysteresis_ws_bytes": (c_i64, [c_i32, c_i32, c_i32]),
+    "omg_canny_hysteresis": (c_i32, [c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
     "omg_debug_set_glds": (None, [c_i32]),
     "omg_debug_set_gemm_variant": (None, [c_i32]),
     "omg_debug_choose_variant": (c_i32, [c_i32, c_i32, c_i32, c_i32]),

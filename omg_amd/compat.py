@@ -469,7 +469,7 @@ def install(stub_missing: bool = True) -> List[str]:
     import runpy; runpy.run_path('inference_lora.py', run_name='__main__')"``) is the whole edit.  Call it BEFORE the script's imports; it
     overrides a real ``diffusers`` for the process (that is its purpose).  ``stub_missing``: third-party modules of the import block that
     are outside the hot path and absent from the environment get stand-ins — ``torchvision.utils.save_image`` (a real implementation
-    on PIL), ``cv2`` / ``insightface.app.FaceAnalysis`` (importable; using them raises).  Returns the names it registered."""
+    on PIL), ``cv2`` / ``insightface.app.FaceAnalysis`` (importable; using them raises, but for ``cv2.Canny``: omg_amd.canny.Canny).  Returns the names it registered."""
     import importlib
     import importlib.util
     import sys
@@ -555,6 +555,8 @@ def install(stub_missing: bool = True) -> List[str]:
         if absent("cv2"):
             cv2 = module("cv2")
             cv2.__getattr__ = lambda a: _Unavailable("cv2").__getattr__(a)          # PEP 562: any use says what is missing
+            from .canny import Canny
+            cv2.Canny = Canny                   # the one call of the demos' get_cannyedge, on HIP kernels (omg_amd/canny.py)
         if absent("insightface"):
             module("insightface.app", FaceAnalysis=_Unavailable("insightface.app.FaceAnalysis"))
     return done

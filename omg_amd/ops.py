@@ -1713,6 +1713,84 @@ def image_prep(u8: torch.Tensor, out_hw: Tuple[int, int], resample: int, lut: Op
     return out if batched else out[0]
 
 
+# ------------------------------------------------------------------ Canny edge condition (omg_amd/canny.py has the arithmetic)
+def _canny_u8(what: str, t, dims: str) -> None:
+    if not isinstance(t, torch.Tensor):
+        raise L.OmgHipError(f"{what} takes a contiguous cuda uint8 {dims} tensor, got {type(t).__name__}")
+    if not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous() or t.numel() == 0:
+        raise L.OmgHipError(f"{what} takes a contiguous cuda uint8 {dims} tensor, got {t.dtype} {tuple(t.shape)} on {t.device}"
+                            f"{'' if t.is_contiguous() else ', not contiguous'}")
+
+
+def _canny_thresholds(what: str, t1, t2) -> Tuple[int, int]:
+    from . import canny as cn
+    try:
+        return cn.thresholds(t1, t2)
+    except (TypeError, ValueError) as e:
+        raise L.OmgHipError(f"{what}: thresholds ({t1!r}, {t2!r}): {e}") from None
+
+
+def canny_nms(u8: torch.Tensor, low, high) -> torch.Tensor:
+    """Sobel gradients, channel selection and non-maximum suppression of ``cv2.Canny`` in one launch (omg_canny_nms): a contiguous cuda
+    uint8 ``[H, W]``, ``[H, W, C]`` or ``[B, H, W, C]`` image (C 1 or 3) -> the uint8 state map ``[H, W]`` / ``[B, H, W]``: 0 not an edge,
+    1 kept and weak (``mag <= high``), 2 kept and strong.  ``low`` / ``high``: cv2's two thresholds (swapped if need be, floored)."""
+    dims = "[H, W], [H, W, C] or [B, H, W, C] (C 1 or 3)"
+    _canny_u8("canny_nms", u8, dims)
+    if u8.dim() not in (2, 3, 4) or (u8.dim() >= 3 and u8.shape[-1] not in (1, 3)):
+        raise L.OmgHipError(f"canny_nms takes a contiguous cuda uint8 {dims} tensor, got {tuple(u8.shape)}"
+                            + (f": C = {u8.shape[-1]}" if u8.dim() >= 3 else ""))
+    lo, hi = _canny_thresholds("canny_nms", low, high)
+    Cn = 1 if u8.dim() == 2 else int(u8.shape[-1])
+    B = int(u8.shape[0]) if u8.dim() == 4 else 1
+    H, W = (int(u8.shape[0]), int(u8.shape[1])) if u8.dim() == 2 else (int(u8.shape[-3]), int(u8.shape[-2]))
+    state = torch.empty((B, H, W) if u8.dim() == 4 else (H, W), dtype=torch.uint8, device=u8.device)
+    L.check(L.lib().omg_canny_nms(B, H, W, Cn, u8.data_ptr(), lo, hi, state.data_ptr(), _stream()), "omg_canny_nms")
+    return state
+
+
+def canny_hysteresis(state: torch.Tensor, channels: int = 1, out_dtype: Optional[torch.dtype] = None, check: bool = True) -> torch.Tensor:
+    """Hysteresis of ``cv2.Canny`` on a state map (omg_canny_hysteresis): a contiguous cuda uint8 ``[H, W]`` / ``[B, H, W]`` map of 0, 1
+    and 2 -> the pixels of non-zero state whose 8-connected component holds a 2.  ``out_dtype`` None or uint8: uint8 0 / 255,
+    ``[(B,) H, W]`` (``channels=1``) or ``[(B,) H, W, 3]`` (``channels=3``: the same byte three times); float16 / bfloat16 / float32: planar
+    ``[(B,) 3, H, W]`` of 0 and 1.  Four launches and a workspace allocated per call, no host synchronisation: capturable.  ``check``
+    reads the map's maximum back to refuse a value above 2; it is skipped while a graph is being captured."""
+    _canny_u8("canny_hysteresis", state, "[H, W] or [B, H, W] state map")
+    if state.dim() not in (2, 3):
+        raise L.OmgHipError(f"canny_hysteresis takes a contiguous cuda uint8 [H, W] or [B, H, W] state map, got {tuple(state.shape)}")
+    if channels not in (1, 3):
+        raise L.OmgHipError(f"canny_hysteresis: channels={channels!r}, expected 1 or 3")
+    planar = out_dtype is not None and out_dtype != torch.uint8
+    if planar and out_dtype not in _LUT_DT:
+        raise L.OmgHipError(f"canny_hysteresis: out_dtype {out_dtype}, expected uint8 (or None), float16, bfloat16 or float32")
+    if check and not torch.cuda.is_current_stream_capturing():
+        top = int(state.max())
+        if top > 2:
+            raise L.OmgHipError(f"canny_hysteresis: the state map holds the value {top}; states are 0 (none), 1 (weak) and 2 (strong)")
+    batched = state.dim() == 3
+    B = int(state.shape[0]) if batched else 1
+    H, W = int(state.shape[-2]), int(state.shape[-1])
+    if planar:
+        form, code, shape, dt = 2, _LUT_DT[out_dtype], (B, 3, H, W), out_dtype
+    elif channels == 3:
+        form, code, shape, dt = 1, 0, (B, H, W, 3), torch.uint8
+    else:
+        form, code, shape, dt = 0, 0, (B, H, W), torch.uint8
+    lib = L.lib()
+    nbytes = int(lib.omg_canny_hysteresis_ws_bytes(B, H, W))
+    if nbytes <= 0:
+        raise L.OmgHipError(f"canny_hysteresis: sizes {(B, H, W)}: B <= 65535, H <= 16 * 65535 and B H W < 2^29")
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=state.device)          # per call: see _gn_workspace
+    out = torch.empty(shape, dtype=dt, device=state.device)
+    L.check(lib.omg_canny_hysteresis(B, H, W, state.data_ptr(), ws.data_ptr(), form, code, out.data_ptr(), _stream()), "omg_canny_hysteresis")
+    return out if batched else out[0]
+
+
+def canny(u8: torch.Tensor, threshold1, threshold2, channels: int = 1, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """``cv2.Canny(image, threshold1, threshold2)`` (apertureSize 3, L1 gradient) of a contiguous cuda uint8 ``[H, W]``, ``[H, W, C]`` or
+    ``[B, H, W, C]`` image: canny_nms then canny_hysteresis, five launches, nothing on the host.  The output forms are canny_hysteresis's."""
+    return canny_hysteresis(canny_nms(u8, threshold1, threshold2), channels=channels, out_dtype=out_dtype, check=False)
+
+
 # ------------------------------------------------------------------ LoRA bank build: weight-slot merge
 _LORA_KINDS = {"plain": L.LORA_PLAIN, "hada": L.LORA_HADA, "kron": L.LORA_KRON}
 
