@@ -1,7 +1,14 @@
 """Checkpoint plumbing the models share: the reader of a local checkpoint directory, the parameter holders of the models that keep the
-checkpoint's module tree (``param``, ``Weight``, ``Seq``), and :class:`FlatWeights`, the base of the models that keep their parameters in
-one flat dict under the checkpoint's key names (``SwinBackbone``, ``BertTextEncoder``, ``GroundingDinoEncoder``,
-``GroundingDinoDecoderHead``).  No kernel is called from here.
+checkpoint's module tree (``param``, ``Weight``, ``Seq``), :class:`PackedCache`, the base of every module that keeps operands derived
+from its weights, and :class:`FlatWeights`, the base of the models that keep their parameters in one flat dict under the checkpoint's
+key names (``SwinBackbone``, ``BertTextEncoder``, ``GroundingDinoEncoder``, ``GroundingDinoDecoderHead``).  No kernel is called from here.
+
+The derived-operand contract.  Fused q|k|v stacks, BatchNorm-folded and repacked convolution weights, the dense positional encoding and
+their like are computed once from the weights and reused by every forward; their holder is a :class:`PackedCache` and drops them in
+``invalidate_packed()``.  The base calls that from ``_load_from_state_dict`` and ``_apply`` — the two hooks torch runs on EVERY
+descendant, whichever module ``load_state_dict``, ``.to()`` or ``.half()`` was called on — and nowhere else in the package is the rule
+written: no holder overrides ``load_state_dict`` for it, and nobody assigns another module's cache.  No hook sees an in-place write to
+a parameter (``p.data.copy_(...)``): whoever writes one calls ``invalidate_packed()`` afterwards, as the ``init_synthetic_`` methods do.
 """
 from __future__ import annotations
 
@@ -14,7 +21,7 @@ import torch.nn as nn
 
 from . import _lib as L
 
-__all__ = ["read_checkpoint", "param", "Weight", "Seq", "FlatWeights"]
+__all__ = ["read_checkpoint", "param", "Weight", "Seq", "PackedCache", "FlatWeights"]
 
 
 def read_checkpoint(path, who):
@@ -64,8 +71,40 @@ class Seq(nn.Module):
         return getattr(self, str(i))
 
 
+# ------------------------------------------------------------------------------------------------ operands derived from the weights
+class PackedCache(nn.Module):
+    """A module that keeps ``self._packed``: kernel operands derived from its weights, built once by ``_pk()`` from ``_pack()`` and
+    dropped by ``invalidate_packed()`` whenever a state dict is loaded or the module is moved or cast, through whichever ancestor.
+    Falsy (None, {}) means not built.  A holder that builds everything at once returns the whole dict from ``_pack()``; one that
+    fills per key keeps the default and fills the dict ``_pk()`` hands it.  A subclass that derives more than ``_packed`` from its
+    weights extends ``invalidate_packed()``."""
+
+    def __init__(self):
+        super().__init__()
+        self._packed: Optional[dict] = None
+
+    def _pack(self) -> dict:
+        return {}
+
+    def _pk(self) -> dict:
+        if not self._packed:
+            self._packed = self._pack()
+        return self._packed
+
+    def invalidate_packed(self) -> None:
+        self._packed = None
+
+    def _load_from_state_dict(self, *a, **k):
+        self.invalidate_packed()
+        return super()._load_from_state_dict(*a, **k)
+
+    def _apply(self, fn, *a, **k):
+        self.invalidate_packed()
+        return super()._apply(fn, *a, **k)
+
+
 # ------------------------------------------------------------------------------------------------ parameters in one flat dict
-class FlatWeights(nn.Module):
+class FlatWeights(PackedCache):
     """An inference-only module whose parameters are ``self._w``: one dict of tensors under the checkpoint's own key names, in the order
     and with the shapes of ``shapes()``.  A model supplies ``check_config`` (a static method: the checkpoint's config -> the dict kept as
     ``self.cfg``), ``shapes()``, ``_pack()`` (the kernel operands that are not the checkpoint's own tensors; ``_pk()`` builds them once
@@ -83,7 +122,6 @@ class FlatWeights(nn.Module):
         self.cfg = self.check_config(config)
         self._dtype, self._device = dtype, torch.device(device) if device is not None else torch.device("cpu")
         self._w: Dict[str, torch.Tensor] = {k: torch.zeros(s, dtype=dtype, device=self._device) for k, s in self.shapes().items()}
-        self._packed: Optional[dict] = None
         self.eval()
 
     def shapes(self) -> Dict[str, tuple]:
@@ -91,11 +129,6 @@ class FlatWeights(nn.Module):
 
     def _pack(self) -> dict:
         raise NotImplementedError
-
-    def _pk(self) -> dict:
-        if self._packed is None:
-            self._packed = self._pack()
-        return self._packed
 
     def state_dict(self, *a, **k):
         return dict(self._w)
@@ -139,7 +172,7 @@ class FlatWeights(nn.Module):
         if strict and (missing or unexpected):
             raise L.OmgHipError(f"{who}.load_state_dict: missing {missing[:6]}{' ...' if len(missing) > 6 else ''}, "
                                 f"unexpected {unexpected[:6]}{' ...' if len(unexpected) > 6 else ''}")
-        self._packed = None
+        self.invalidate_packed()
         return missing, unexpected
 
     @classmethod
@@ -165,7 +198,7 @@ class FlatWeights(nn.Module):
     def _apply(self, fn, *a, **k):
         self._w = {key: fn(t) for key, t in self._w.items()}
         any_t = next(iter(self._w.values()))
-        self._dtype, self._device, self._packed = any_t.dtype, any_t.device, None
+        self._dtype, self._device = any_t.dtype, any_t.device
         return super()._apply(fn, *a, **k)
 
     @property

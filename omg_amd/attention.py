@@ -31,10 +31,11 @@ from torch import nn
 
 from . import _lib as L
 from . import ops
+from ._checkpoint import PackedCache
 from .modules import Dropout, Linear, LoraState, bump_pointer_epoch, pointer_epoch  # noqa: F401
 
 
-class Attention(nn.Module):
+class Attention(PackedCache):
     """The slice of ``diffusers.models.attention_processor.Attention`` that OMG touches."""
 
     def __init__(self, query_dim: int, cross_attention_dim: Optional[int], heads: int, dim_head: int = 64,
@@ -99,12 +100,9 @@ class Attention(nn.Module):
         q, k = query.contiguous(), key.contiguous()
         return ops.attn_probs(q, k, 1, self.scale)      # batch' = B*heads, one head of 64
 
-    def _apply(self, fn, *a, **k):        # .to() / .half(): the fused weight images and K/V caches belong to the old storage
-        self.invalidate_packed()
-        return super()._apply(fn, *a, **k)
-
     # ---- fused projections
-    def invalidate_packed(self):
+    def invalidate_packed(self):          # a load, .to() / .half(): the fused weight images and K/V caches belong to the old weights
+        super().invalidate_packed()
         self._qkv = self._kv = self._qkv_slots = self._kv_slots = None
         self._kv_cache = {}
         self._mx8 = {}

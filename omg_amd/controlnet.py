@@ -23,6 +23,7 @@ from torch import nn
 
 from . import _lib as L
 from . import ops
+from ._checkpoint import PackedCache
 from .attention import Attention
 from .modules import Conv2d, bump_pointer_epoch, bump_weights_version
 from .unet import (CrossAttnDownBlock2D, DownBlock2D, TimestepEmbedding, UNetConfig, UNetMidBlock2DCrossAttn, _Ctx)
@@ -34,7 +35,7 @@ def _pad64(c: int) -> int:
     return (c + 63) // 64 * 64
 
 
-class ControlNetConditioningEmbedding(nn.Module):
+class ControlNetConditioningEmbedding(PackedCache):
     def __init__(self, out_channels: int, cond_in: int, dtype, device):
         super().__init__()
         self.conv_in = Conv2d(cond_in, COND_CHANNELS[0], 3, dtype=dtype, device=device)
@@ -43,14 +44,11 @@ class ControlNetConditioningEmbedding(nn.Module):
             self.blocks.append(Conv2d(COND_CHANNELS[i], COND_CHANNELS[i], 3, dtype=dtype, device=device))
             self.blocks.append(Conv2d(COND_CHANNELS[i], COND_CHANNELS[i + 1], 3, stride=2, dtype=dtype, device=device))
         self.conv_out = Conv2d(COND_CHANNELS[-1], out_channels, 3, dtype=dtype, device=device)
-        self._pk = {}
-
-    def invalidate_packed(self):
-        self._pk = {}
 
     def _padded(self, name: str, conv: Conv2d, pad_out: bool):
         """[Cout_p][3][3][Cin_p] weight and [Cout_p] bias with channels zero-padded to multiples of 64."""
-        if name not in self._pk:
+        pk = self._pk()
+        if name not in pk:
             w = conv.weight.data
             co, ci = w.shape[:2]
             cop = _pad64(co) if pad_out else co
@@ -58,8 +56,8 @@ class ControlNetConditioningEmbedding(nn.Module):
             wp[:co, :, :, :ci] = w.permute(0, 2, 3, 1)
             bp = torch.zeros((cop,), dtype=w.dtype, device=w.device)
             bp[:co] = conv.bias.data
-            self._pk[name] = (wp.reshape(cop, -1).contiguous(), bp)
-        return self._pk[name]
+            pk[name] = (wp.reshape(cop, -1).contiguous(), bp)
+        return pk[name]
 
     def forward(self, cond_nchw: torch.Tensor) -> torch.Tensor:
         """cond (B,3,H,W) in [0,1] -> NHWC (B,H/8,W/8,C0)."""
@@ -76,7 +74,7 @@ class ControlNetConditioningEmbedding(nn.Module):
         return ops.conv2d(x, w, 3, bias=b)
 
 
-class ControlNetModel(nn.Module):
+class ControlNetModel(PackedCache):
     def __init__(self, config: Optional[UNetConfig] = None, dtype: torch.dtype = torch.float16, device=None,
                  conditioning_channels: int = 3):
         super().__init__()
@@ -102,7 +100,6 @@ class ControlNetModel(nn.Module):
         self.mid_block = UNetMidBlock2DCrossAttn(cfg, dtype, device)
         self.controlnet_down_blocks = nn.ModuleList([Conv2d(c, c, 1, dtype=dtype, device=device) for c in chans])
         self.controlnet_mid_block = Conv2d(cfg.block_out_channels[-1], cfg.block_out_channels[-1], 1, dtype=dtype, device=device)
-        self._boundary = {}
         self._cond_cache = None
 
     @property
@@ -114,22 +111,19 @@ class ControlNetModel(nn.Module):
         return self.conv_in.weight.device
 
     def invalidate_packed(self):
-        self._boundary = {}
+        """Tree-wide, as the UNet's."""
+        super().invalidate_packed()
         self._cond_cache = None
         for m in self.modules():
             if m is not self and hasattr(m, "invalidate_packed"):
                 m.invalidate_packed()
 
-    def _apply(self, fn, *a, **k):
-        self._boundary = {}
-        self._cond_cache = None
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, *a, **k):
-        r = super().load_state_dict(*a, **k)
-        self.invalidate_packed()
+    def _load_from_state_dict(self, *a, **k):       # once per load, whichever module ``load_state_dict`` was called on
         bump_weights_version(self)
-        return r
+        return super()._load_from_state_dict(*a, **k)
+
+    def _pack(self):
+        return {"in": ops.pack_conv_in_weight(self.conv_in.weight.data)}
 
     # the time/text embedding is the UNet's; reuse its implementation
     from .unet import UNet2DConditionModel as _U
@@ -190,8 +184,6 @@ class ControlNetModel(nn.Module):
         if ehs.dtype != dt or not ehs.is_contiguous():
             ehs = ehs.to(dt).contiguous()
         ctx = _Ctx(ops.silu(emb), ehs, B)
-        if not self._boundary:
-            self._boundary["in"] = ops.pack_conv_in_weight(self.conv_in.weight.data)
         x_in = sample.contiguous()
         if x_in.dtype not in (torch.float32, dt):
             x_in = x_in.to(dt)
@@ -200,7 +192,7 @@ class ControlNetModel(nn.Module):
             if B % cond.shape[0] != 0:
                 raise ValueError("controlnet_cond batch does not divide the sample batch")
             cond = cond.repeat_interleave(B // cond.shape[0], dim=0)      # each conditioning image covers a block of consecutive rows
-        h = ops.conv_in(x_in, self._boundary["in"], self.conv_in.bias, dt)
+        h = ops.conv_in(x_in, self._pk()["in"], self.conv_in.bias, dt)
         h = ops.add_(h, cond.contiguous())
         skips: List[torch.Tensor] = [h]
         for blk in self.down_blocks:

@@ -31,7 +31,7 @@ import json
 import math
 import os
 from types import SimpleNamespace
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Dict, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -39,7 +39,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ops
-from ._checkpoint import Weight as _W, param as _param, read_checkpoint
+from ._checkpoint import PackedCache, Weight as _W, param as _param, read_checkpoint
 
 __all__ = ["DPTForDepthEstimation", "DPTImageProcessor", "DPTFeatureExtractor", "depth_condition", "check_config", "fold_weight_standardization"]
 
@@ -166,7 +166,7 @@ class DepthEstimatorOutput(SimpleNamespace):
     """``.predicted_depth`` (and ``.features`` when asked for)."""
 
 
-class DPTForDepthEstimation(nn.Module):
+class DPTForDepthEstimation(PackedCache):
     def __init__(self, config: dict, dtype=torch.float16, device=None):
         super().__init__()
         cfg = self.cfg = check_config(config)
@@ -197,7 +197,6 @@ class DPTForDepthEstimation(nn.Module):
         self.head = _Holder(head=_mlist([_W((F // 2, F, 3, 3), F // 2, dt, dev), nn.Identity(), _W((32, F // 2, 3, 3), 32, dt, dev), nn.Identity(),
                                          _W((1, 32, 1, 1), 1, dt, dev), nn.Identity()]))
         self.num_groups, self.grid = G, grid
-        self._packed: Optional[dict] = None
         self._folded: Dict[str, torch.Tensor] = {}          # fp32 folds of the weight-standardised convolutions, from the checkpoint's own precision
 
     # ------------------------------------------------------------------ loading
@@ -212,18 +211,12 @@ class DPTForDepthEstimation(nn.Module):
     def _ws_keys(self):
         return [k for k in self.state_dict() if ".backbone.bit." in k and k.endswith(".weight") and (".conv" in k or k.endswith("convolution.weight"))]
 
-    def load_state_dict(self, state_dict, *a, **k):
-        self._packed = None
-        dev = self.dpt.layernorm.weight.device
-        self._folded = {key: fold_weight_standardization(state_dict[key]).to(dev) for key in self._ws_keys() if key in state_dict}
-        return super().load_state_dict(state_dict, *a, **k)
-
-    def _apply(self, fn, *a, **k):
-        self._packed = None
-        out = super()._apply(fn, *a, **k)
-        dev = self.dpt.layernorm.weight.device
-        self._folded = {key: v.to(dev) for key, v in self._folded.items()}
-        return out
+    def _load_from_state_dict(self, state_dict, prefix, *a, **k):
+        """The folds are taken here, from the incoming tensors in their own precision, so that a load through a parent refolds too; they
+        are kept on the weights' device, stay fp32 through ``.to()`` and follow a later move when they are packed."""
+        dev = self.device
+        self._folded = {key: fold_weight_standardization(state_dict[prefix + key]).to(dev) for key in self._ws_keys() if prefix + key in state_dict}
+        return super()._load_from_state_dict(state_dict, prefix, *a, **k)
 
     @property
     def dtype(self):
@@ -234,16 +227,14 @@ class DPTForDepthEstimation(nn.Module):
         return self.dpt.layernorm.weight.device
 
     # ------------------------------------------------------------------ kernel operands that are not the checkpoint's own tensors, built once
-    def _pk(self) -> dict:
-        if self._packed is not None:
-            return self._packed
-        dt = self.dtype
+    def _pack(self) -> dict:
+        dt, dev = self.dtype, self.device
         sd = dict(self.state_dict())
         pk: dict = {}
 
         def ws(key):                                       # folded in fp32 (from the checkpoint's tensor when it was loaded), rounded once
             f = self._folded.get(key)
-            return (f if f is not None else fold_weight_standardization(sd[key])).to(dt)
+            return (f if f is not None else fold_weight_standardization(sd[key])).to(device=dev, dtype=dt)
 
         def k33(w):
             return w.permute(0, 2, 3, 1).contiguous()
@@ -283,7 +274,6 @@ class DPTForDepthEstimation(nn.Module):
                     pk[f"fu{i}.{u}.{c}"] = k33(getattr(getattr(ly, u), c).weight.data)
         h = self.head.head
         pk["head0"], pk["head2"], pk["head4"] = k33(h[0].weight.data), k33(h[2].weight.data), h[4].weight.data.reshape(-1).contiguous()
-        self._packed = pk
         return pk
 
     # ------------------------------------------------------------------ forward

@@ -30,6 +30,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ops
+from ._checkpoint import PackedCache
 from .litemla import LiteMLA
 
 
@@ -237,7 +238,7 @@ class _LayerNorm(nn.Module):
 
 
 # ---------------------------------------------------------------------------------------------- the encoder
-class EfficientViTSamImageEncoder(nn.Module):
+class EfficientViTSamImageEncoder(PackedCache):
     def __init__(self, variant: Union[str, EfficientViTSamConfig] = "l0", dtype=torch.float16, device=None):
         super().__init__()
         cfg = variant if isinstance(variant, EfficientViTSamConfig) else EfficientViTSamConfig.variant(variant)
@@ -248,21 +249,13 @@ class EfficientViTSamImageEncoder(nn.Module):
         self.backbone = _Backbone(cfg, dtype, device)
         self.neck = _Neck(cfg, dtype, device)
         self.norm = _LayerNorm(cfg.out_dim, dtype, device)
-        self._packed: Dict[int, tuple] = {}
 
-    # ------------------------------------------------------------------ packed (BatchNorm-folded) weights, built once
-    def load_state_dict(self, *a, **k):
-        self._packed = {}
-        return super().load_state_dict(*a, **k)
-
-    def _apply(self, fn, *a, **k):
-        self._packed = {}
-        return super()._apply(fn, *a, **k)
-
+    # ------------------------------------------------------------------ packed (BatchNorm-folded) weights, built once per layer
     def _pk(self, layer: ConvLayer):
-        p = self._packed.get(id(layer))
+        pk = super()._pk()
+        p = pk.get(id(layer))
         if p is None:
-            p = self._packed[id(layer)] = layer.packed()
+            p = pk[id(layer)] = layer.packed()
         return p
 
     # ------------------------------------------------------------------ blocks on NHWC tensors

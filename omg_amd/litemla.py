@@ -26,6 +26,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ops
+from ._checkpoint import PackedCache
 
 
 class _Conv(nn.Module):
@@ -51,7 +52,7 @@ class _ConvLayer(nn.Module):
             self.norm.eps = 1e-5
 
 
-class LiteMLA(nn.Module):
+class LiteMLA(PackedCache):
     def __init__(self, in_channels: int, out_channels: int, heads: Optional[int] = None, heads_ratio: float = 1.0, dim: int = 8,
                  use_bias=False, norm=(None, "bn2d"), act_func=(None, None), kernel_func: str = "relu", scales: Sequence[int] = (5,),
                  eps: float = 1.0e-15, dtype=torch.float16, device=None, aggreg: str = "gemm"):
@@ -72,24 +73,9 @@ class LiteMLA(nn.Module):
         self.aggreg = nn.ModuleList([nn.ModuleList([_Conv((3 * T, 1, s, s), dtype, device), _Conv((3 * T, dim, 1, 1), dtype, device)])
                                      for s in self.scales])
         self.proj = _ConvLayer(T * (1 + len(self.scales)), out_channels, norm[1] == "bn2d", dtype, device)
-        self._packed = {}
 
-    # ------------------------------------------------------------------ derived weight images (built once)
-    def _load_from_state_dict(self, *a, **k):
-        self._packed = {}
-        return super()._load_from_state_dict(*a, **k)
-
-    def load_state_dict(self, *a, **k):
-        self._packed = {}
-        return super().load_state_dict(*a, **k)
-
-    def _apply(self, fn, *a, **k):
-        self._packed = {}
-        return super()._apply(fn, *a, **k)
-
+    # ------------------------------------------------------------------ derived weight images (built once: PackedCache._pk)
     def _pack(self):
-        if self._packed:
-            return self._packed
         T3, d = 3 * self.total_dim, self.dim
         dt = self.qkv.conv.weight.dtype
         pk = {"wqkv": self.qkv.conv.weight.data.reshape(T3, self.in_channels).contiguous(), "taps": []}
@@ -109,7 +95,6 @@ class LiteMLA(nn.Module):
             w = w * a[:, None]
             bias = (n.bias.data.float() - n.running_mean.float() * a).to(dt)
         pk["wproj"], pk["bproj"] = w.to(dt).contiguous(), bias
-        self._packed = pk
         return pk
 
     # ------------------------------------------------------------------ forward
@@ -117,7 +102,7 @@ class LiteMLA(nn.Module):
         """x (B, H, W, Cin) contiguous -> (B, H, W, Cout)."""
         B, H, W, Cin = x.shape
         assert Cin == self.in_channels and x.is_contiguous()
-        pk = self._pack()
+        pk = self._pk()
         M, T3, n = B * H * W, 3 * self.total_dim, len(self.scales)
         x2 = x.view(M, Cin)
         buf = torch.empty((M, T3 * (1 + n)), dtype=x.dtype, device=x.device)

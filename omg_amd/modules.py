@@ -6,8 +6,8 @@ checkpoints load"); every ``forward`` dispatches to a HIP kernel through :mod:`o
 Activations are NHWC / token-major ``(B, H*W, C)`` everywhere inside the network.
 
 Derived weight images (conv weights repacked to ``[Cout][ky][kx][Cin]``, GEGLU rows interleaved,
-q|k|v concatenated) are built lazily from the canonical parameters and invalidated by
-``load_state_dict`` / ``invalidate_packed``.
+q|k|v concatenated) are built lazily from the canonical parameters and dropped by
+``invalidate_packed`` (``_checkpoint.PackedCache``: every load, move or cast calls it).
 """
 from __future__ import annotations
 
@@ -18,6 +18,7 @@ from torch import nn
 
 from . import _lib as L
 from . import ops
+from ._checkpoint import PackedCache
 
 
 class LoraState:
@@ -53,7 +54,10 @@ def bump_pointer_epoch() -> None:
     _POINTER_EPOCH[0] += 1
 
 
-class _Packed(nn.Module):
+class _Packed(PackedCache):
+    """The holders captured step graphs point into: ``_packed`` is always a dict, which the layers index and fill per key, and dropping
+    a filled one moves the pointer epoch."""
+
     def __init__(self):
         super().__init__()
         self._packed = {}
@@ -62,14 +66,6 @@ class _Packed(nn.Module):
         if self._packed:
             bump_pointer_epoch()
         self._packed = {}
-
-    def _load_from_state_dict(self, *a, **k):
-        self.invalidate_packed()
-        return super()._load_from_state_dict(*a, **k)
-
-    def _apply(self, fn, *a, **k):
-        self.invalidate_packed()
-        return super()._apply(fn, *a, **k)
 
 
 class Linear(_Packed):
@@ -165,9 +161,6 @@ class GEGLU(_Packed):
             if self.proj.w_slots is not None:
                 self._packed["w_slots"] = self.proj.w_slots[:, perm].contiguous()
         return self._packed
-
-    def invalidate_packed(self):
-        super().invalidate_packed()
 
     def _forward_mx8(self, x, out_mx8: bool = False):
         xq = x if isinstance(x, ops.Mx8Tensor) else ops.quant_mx8(x)

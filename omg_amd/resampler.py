@@ -14,6 +14,7 @@ from torch import nn
 
 from . import _lib as L
 from . import ops
+from ._checkpoint import PackedCache
 from .modules import LayerNorm, Linear
 
 
@@ -29,7 +30,7 @@ class _PerceiverAttention(nn.Module):
         self.to_out = Linear(inner, dim, bias=False, dtype=dtype, device=device)
 
 
-class Resampler(nn.Module):
+class Resampler(PackedCache):
     def __init__(self, dim=1280, depth=4, dim_head=64, heads=20, num_queries=16, embedding_dim=512, output_dim=2048, ff_mult=4,
                  dtype=torch.float16, device="cuda"):
         super().__init__()
@@ -46,17 +47,9 @@ class Resampler(nn.Module):
                            nn.ModuleList([LayerNorm(dim, 1e-5, dtype=dtype, device=device), Linear(dim, ff, bias=False, dtype=dtype, device=device),
                                           nn.Identity(), Linear(ff, dim, bias=False, dtype=dtype, device=device)])])
             for _ in range(depth)])
-        self._ff_packed = None
-
-    def load_state_dict(self, *a, **k):
-        self._ff_packed = None
-        return super().load_state_dict(*a, **k)
-
-    def _apply(self, fn, *a, **k):
-        self._ff_packed = None
-        return super()._apply(fn, *a, **k)
 
     def _pack(self):
+        """Per layer, the feed-forward's first Linear as a GEGLU GEMM with a constant-one value half."""
         out = []
         for _, ff in self.layers:
             w1 = ff[1].weight.data
@@ -65,21 +58,19 @@ class Resampler(nn.Module):
             wg = torch.cat([torch.zeros_like(w1), w1])[perm].contiguous()
             bg = torch.cat([torch.ones(f, dtype=w1.dtype, device=w1.device), torch.zeros(f, dtype=w1.dtype, device=w1.device)])[perm].contiguous()
             out.append((wg, bg))
-        self._ff_packed = out
+        return out
 
     @torch.no_grad()
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """x: (B, n1, embedding_dim) -> (B, num_queries, output_dim)."""
         if not x.is_cuda:
             raise L.OmgHipError("Resampler runs on the HIP kernels only (no CPU fallback)")
-        if self._ff_packed is None:
-            self._pack()
         B, n1, _ = x.shape
         Q, D, heads = self.num_queries, self.dim, self.heads
         inner = 64 * heads
         xs = self.proj_in(x.to(self._dtype).reshape(B * n1, -1).contiguous())
         lat = self.latents.data.expand(B, Q, D).reshape(B * Q, D).contiguous()
-        for (attn, ff), (wg, bg) in zip(self.layers, self._ff_packed):
+        for (attn, ff), (wg, bg) in zip(self.layers, self._pk()):
             xn, ln = attn.norm1(xs), attn.norm2(lat)
             q = attn.to_q(ln).view(B, Q, inner)
             kv_in = torch.cat([xn.view(B, n1, D), ln.view(B, Q, D)], dim=1).reshape(B * (n1 + Q), D).contiguous()

@@ -28,7 +28,7 @@ import torch.nn as nn
 from . import _lib as L
 from . import ops
 from . import efficientvit as _ev
-from ._checkpoint import Seq as _Seq, Weight as _Weight
+from ._checkpoint import PackedCache, Seq as _Seq, Weight as _Weight
 from .efficientvit import EfficientViTSamConfig, EfficientViTSamImageEncoder
 from .litemla import LiteMLA
 
@@ -49,7 +49,7 @@ class _PositionEmbeddingRandom(nn.Module):
         return torch.cat([torch.sin(c), torch.cos(c)], dim=-1)
 
 
-class SamPromptEncoder(nn.Module):
+class SamPromptEncoder(PackedCache):
     def __init__(self, embed_dim: int = 256, image_embedding_size: Tuple[int, int] = (64, 64), input_image_size: Tuple[int, int] = (1024, 1024),
                  mask_in_chans: int = 16, dtype=torch.float16, device=None):
         super().__init__()
@@ -63,15 +63,6 @@ class SamPromptEncoder(nn.Module):
                                       3: _Weight((m, m // 4, 2, 2), m, dtype, device), 4: _Weight((m,), m, dtype, device),
                                       6: _Weight((embed_dim, m, 1, 1), embed_dim, dtype, device)})
         self.no_mask_embed = _Weight((1, embed_dim), 0, dtype, device)
-        self._dense_pe: Dict[tuple, torch.Tensor] = {}
-
-    def load_state_dict(self, *a, **k):
-        self._dense_pe = {}
-        return super().load_state_dict(*a, **k)
-
-    def _apply(self, fn, *a, **k):
-        self._dense_pe = {}
-        return super()._apply(fn, *a, **k)
 
     @property
     def dtype(self):
@@ -80,22 +71,22 @@ class SamPromptEncoder(nn.Module):
     def get_dense_pe(self) -> torch.Tensor:
         """The positional encoding of the embedding grid as NHWC rows [H * W, embed_dim] in the storage dtype; computed once."""
         g = self.pe_layer.positional_encoding_gaussian_matrix
-        key = (g.device, self.dtype)
-        pe = self._dense_pe.get(key)
+        key, pk = (g.device, self.dtype), self._pk()         # the dense encoding and ``_coords``' constant, per device and dtype
+        pe = pk.get(key)
         if pe is None:
             h, w = self.image_embedding_size
             y = (torch.arange(h, device=g.device, dtype=torch.float32) + 0.5) / h
             x = (torch.arange(w, device=g.device, dtype=torch.float32) + 0.5) / w
             grid = torch.stack([x[None, :].expand(h, w), y[:, None].expand(h, w)], dim=-1)
-            pe = self._dense_pe[key] = self.pe_layer.encode(grid).reshape(h * w, self.embed_dim).to(self.dtype).contiguous()
+            pe = pk[key] = self.pe_layer.encode(grid).reshape(h * w, self.embed_dim).to(self.dtype).contiguous()
         return pe
 
     def _coords(self, pts: torch.Tensor) -> torch.Tensor:
         h, w = self.input_image_size
-        key = ("wh", pts.device)                 # uploaded once: a captured call (GroundedSam.predict_masks) cannot upload it
-        wh = self._dense_pe.get(key)
+        key, pk = ("wh", pts.device), self._pk()  # uploaded once: a captured call (GroundedSam.predict_masks) cannot upload it
+        wh = pk.get(key)
         if wh is None:
-            wh = self._dense_pe[key] = torch.tensor([w, h], dtype=torch.float32, device=pts.device)
+            wh = pk[key] = torch.tensor([w, h], dtype=torch.float32, device=pts.device)
         return self.pe_layer.encode((pts.float() + 0.5) / wh)
 
     @torch.no_grad()
@@ -176,7 +167,7 @@ class _MLP(nn.Module):
         self.layers = nn.ModuleList([_Weight((b, a), b, dtype, device) for a, b in zip(dims[:-1], dims[1:])])
 
 
-class SamMaskDecoder(nn.Module):
+class SamMaskDecoder(PackedCache):
     LN_EPS = 1e-5            # nn.LayerNorm's default (set_norm_eps overrides it per instance); LayerNorm2d of output_upscaling uses 1e-6
 
     def __init__(self, transformer_dim: int = 256, num_multimask_outputs: int = 3, depth: int = 2, num_heads: int = 8, mlp_dim: int = 2048,
@@ -193,27 +184,16 @@ class SamMaskDecoder(nn.Module):
                                       3: _Weight((D // 4, D // 8, 2, 2), D // 8, dtype, device)})
         self.output_hypernetworks_mlps = nn.ModuleList([_MLP(D, D, D // 8, 3, dtype, device) for _ in range(self.num_mask_tokens)])
         self.iou_prediction_head = _MLP(D, iou_head_hidden_dim, self.num_mask_tokens, iou_head_depth, dtype, device)
-        self._packed: Optional[dict] = None
 
-    def load_state_dict(self, *a, **k):
-        self._packed = None
-        return super().load_state_dict(*a, **k)
-
-    def _apply(self, fn, *a, **k):
-        self._packed = None
-        return super()._apply(fn, *a, **k)
-
-    def _pk(self) -> dict:
+    def _pack(self) -> dict:
         """GEMM operands that are not the checkpoint's own tensors: transposed-convolution weights and the IoU head's last layer,
         padded from num_mask_tokens to omg_gemm's 8 output columns."""
-        if self._packed is None:
-            last = self.iou_prediction_head.layers[-1]
-            w = torch.zeros((8, last.weight.shape[1]), dtype=last.weight.dtype, device=last.weight.device)
-            b = torch.zeros((8,), dtype=last.weight.dtype, device=last.weight.device)
-            w[:self.num_mask_tokens], b[:self.num_mask_tokens] = last.weight.data, last.bias.data
-            self._packed = {"up0": ops.pack_convt2x2_weight(self.output_upscaling[0].weight.data),
-                            "up3": ops.pack_convt2x2_weight(self.output_upscaling[3].weight.data), "iou_w": w, "iou_b": b}
-        return self._packed
+        last = self.iou_prediction_head.layers[-1]
+        w = torch.zeros((8, last.weight.shape[1]), dtype=last.weight.dtype, device=last.weight.device)
+        b = torch.zeros((8,), dtype=last.weight.dtype, device=last.weight.device)
+        w[:self.num_mask_tokens], b[:self.num_mask_tokens] = last.weight.data, last.bias.data
+        return {"up0": ops.pack_convt2x2_weight(self.output_upscaling[0].weight.data),
+                "up3": ops.pack_convt2x2_weight(self.output_upscaling[3].weight.data), "iou_w": w, "iou_b": b}
 
     # ------------------------------------------------------------------ pieces; x is [B, N, C], a GEMM is run per prompt
     @staticmethod
@@ -414,15 +394,12 @@ def set_norm_eps(model: nn.Module, eps: float) -> None:
     for m in model.modules():
         if isinstance(m, (_ev._BatchNorm, _ev._LayerNorm)):
             m.eps = eps
-        elif isinstance(m, LiteMLA):
-            if m.proj.norm is not None:
-                m.proj.norm.eps = eps
-            m._packed = {}
-        elif isinstance(m, EfficientViTSamImageEncoder):
-            m._packed = {}
+        elif isinstance(m, LiteMLA) and m.proj.norm is not None:
+            m.proj.norm.eps = eps
         elif isinstance(m, SamMaskDecoder):
             m.LN_EPS = eps
-            m._packed = None
+        if isinstance(m, PackedCache):
+            m.invalidate_packed()
 
 
 def create_sam_model(name: str, pretrained: bool = True, weight_url: Optional[str] = None, dtype=torch.float16, device=None) -> EfficientViTSam:

@@ -22,14 +22,14 @@ input sizes other than the model's.  Inference only.  There is no CPU path: ``fo
 from __future__ import annotations
 
 import math
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Dict, Sequence, Tuple
 
 import torch
 import torch.nn as nn
 
 from . import _lib as L
 from . import ops
-from ._checkpoint import Seq as _Seq, Weight as _Weight, param as _param
+from ._checkpoint import PackedCache, Seq as _Seq, Weight as _Weight, param as _param
 
 __all__ = ["SamImageEncoderViT"]
 
@@ -70,7 +70,7 @@ class _Block(nn.Module):
         self.mlp = _MLP(dim, int(dim * mlp_ratio), dtype, device)
 
 
-class SamImageEncoderViT(nn.Module):
+class SamImageEncoderViT(PackedCache):
     LN_EPS = 1e-6
 
     def __init__(self, img_size: int = 1024, patch_size: int = 16, in_chans: int = 3, embed_dim: int = 768, depth: int = 12, num_heads: int = 12,
@@ -90,24 +90,13 @@ class SamImageEncoderViT(nn.Module):
                                      for i in range(depth)])
         self.neck = _Seq([_Weight((out_chans, embed_dim, 1, 1), 0, dtype, device), _Weight((out_chans,), out_chans, dtype, device),
                           _Weight((out_chans, out_chans, 3, 3), 0, dtype, device), _Weight((out_chans,), out_chans, dtype, device)])
-        self._packed: Optional[dict] = None
 
     # ------------------------------------------------------------------ kernel operands that are not the checkpoint's own tensors, built once
-    def load_state_dict(self, *a, **k):
-        self._packed = None
-        return super().load_state_dict(*a, **k)
-
-    def _apply(self, fn, *a, **k):
-        self._packed = None
-        return super()._apply(fn, *a, **k)
-
-    def _pk(self) -> dict:
-        if self._packed is None:
-            D = self.embed_dim
-            self._packed = {"patch": self.patch_embed.proj.weight.data.reshape(D, -1).contiguous(),
-                            "neck0": self.neck[0].weight.data.reshape(self.out_chans, D).contiguous(),
-                            "neck2": self.neck[2].weight.data.permute(0, 2, 3, 1).contiguous()}
-        return self._packed
+    def _pack(self) -> dict:
+        D = self.embed_dim
+        return {"patch": self.patch_embed.proj.weight.data.reshape(D, -1).contiguous(),
+                "neck0": self.neck[0].weight.data.reshape(self.out_chans, D).contiguous(),
+                "neck2": self.neck[2].weight.data.permute(0, 2, 3, 1).contiguous()}
 
     @property
     def dtype(self):

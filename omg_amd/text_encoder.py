@@ -28,6 +28,7 @@ from torch import nn
 
 from . import _lib as L
 from . import ops
+from ._checkpoint import PackedCache
 from .modules import LayerNorm, Linear
 
 
@@ -68,7 +69,7 @@ class _Layer(nn.Module):
         self.mlp.fc2 = Linear(f, d, dtype=dtype, device=device)
 
 
-class ClipTextEncoder(nn.Module):
+class ClipTextEncoder(PackedCache):
     TP = 80          # padded sequence length
 
     def __init__(self, cfg: ClipTextConfig, dtype=torch.float16, device="cuda"):
@@ -88,19 +89,10 @@ class ClipTextEncoder(nn.Module):
             self.text_projection.weight = nn.Parameter(torch.empty(cfg.projection_dim, d, dtype=dtype, device=device), requires_grad=False)
         for p in self.parameters():
             p.requires_grad_(False)
-        self._packed = None
 
     @property
     def device(self):
         return self.text_model.final_layer_norm.weight.device
-
-    def _apply(self, fn, *a, **k):
-        self._packed = None
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, *a, **k):
-        self._packed = None
-        return super().load_state_dict(*a, **k)
 
     def set_lora(self, combo=None) -> None:
         """Activate text-encoder LoRA deltas for the following forwards: ``combo`` = [(weights, multiplier), ...] with
@@ -111,7 +103,8 @@ class ClipTextEncoder(nn.Module):
         combo = [(w, float(m)) for w, m in (combo or []) if w]
         sig = tuple((id(w), m) for w, m in combo)
         if sig != getattr(self, "_lora_sig", ()):
-            self._lora, self._lora_sig, self._packed = combo, sig, None
+            self._lora, self._lora_sig = combo, sig
+            self.invalidate_packed()
 
     def _w(self, li: int, sub: str, lin: Linear) -> torch.Tensor:
         """Weight of ``text_model.encoder.layers.<li>.<sub>`` with the active LoRA deltas merged in."""
@@ -155,7 +148,7 @@ class ClipTextEncoder(nn.Module):
         T = self.TP
         pos = torch.zeros(T, cfg.hidden_size, dtype=dt, device=dev)
         pos[: cfg.max_position_embeddings] = self.text_model.embeddings.position_embedding.weight.data
-        self._packed = {"layers": layers, "pos": pos}
+        return {"layers": layers, "pos": pos}
 
     @torch.no_grad()
     def forward(self, input_ids: torch.Tensor, clip_skip: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -165,9 +158,7 @@ class ClipTextEncoder(nn.Module):
         cfg = self.config
         if not input_ids.is_cuda:
             raise L.OmgHipError("ClipTextEncoder runs on the HIP kernels only (no CPU fallback)")
-        if self._packed is None:
-            self._pack()
-        pk = self._packed
+        pk = self._pk()
         B, T0 = input_ids.shape
         T, d, heads = self.TP, cfg.hidden_size, cfg.num_attention_heads
         if T0 > cfg.max_position_embeddings:

@@ -31,6 +31,7 @@ from torch import nn
 
 from . import _lib as L
 from . import ops
+from ._checkpoint import PackedCache
 from .attention import Attention, FusedAttnProcessor
 from .modules import Conv2d, GEGLU, GroupNorm, LayerNorm, Linear, LoraState, bump_pointer_epoch, bump_weights_version
 
@@ -310,7 +311,7 @@ def set_mx8_classes(net, classes, select=None) -> int:
     return n_on
 
 
-class UNet2DConditionModel(nn.Module):
+class UNet2DConditionModel(PackedCache):
     def __init__(self, config: Optional[UNetConfig] = None, dtype: torch.dtype = torch.float16, device=None):
         super().__init__()
         cfg = config or UNetConfig.sdxl()
@@ -346,7 +347,6 @@ class UNet2DConditionModel(nn.Module):
             self.up_blocks.append(cls(cfg, rev_heads[i], rev_layers[i], prev_c, cout, in_c, typ == "CrossAttnUpBlock2D", i != nb - 1, dtype, device))
         self.conv_norm_out = GroupNorm(cfg.norm_num_groups, c0, cfg.norm_eps, dtype, device)
         self.conv_out = Conv2d(c0, cfg.out_channels, 3, dtype=dtype, device=device)
-        self._boundary = {}
         self._lora_modules: Optional[List[nn.Module]] = None      # Linear and Conv2d: everything that takes a LoraState
 
     # ------------------------------------------------------------------ diffusers-style attributes
@@ -379,20 +379,15 @@ class UNet2DConditionModel(nn.Module):
         self.set_attn_processor(FusedAttnProcessor())
 
     def invalidate_packed(self) -> None:
-        self._boundary = {}
+        """Tree-wide: what follows a write to the parameters that no hook sees (``init_synthetic_``), and every load, move or cast."""
+        super().invalidate_packed()
         for m in self.modules():
             if m is not self and hasattr(m, "invalidate_packed"):
                 m.invalidate_packed()
 
-    def _apply(self, fn, *a, **k):
-        self._boundary = {}
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, *a, **k):
-        r = super().load_state_dict(*a, **k)
-        self.invalidate_packed()
+    def _load_from_state_dict(self, *a, **k):       # once per load, whichever module ``load_state_dict`` was called on
         bump_weights_version(self)
-        return r
+        return super()._load_from_state_dict(*a, **k)
 
     def init_synthetic_(self, seed: int = 0, qk_gain: float = 1.0) -> "UNet2DConditionModel":
         """Seeded random weights ON DEVICE (no SDXL checkpoint is available offline):
@@ -489,11 +484,8 @@ class UNet2DConditionModel(nn.Module):
                 _ip_kv(m, ip_ctx)
 
     # ------------------------------------------------------------------ forward
-    def _boundary_weights(self):
-        if not self._boundary:
-            self._boundary["in"] = ops.pack_conv_in_weight(self.conv_in.weight.data)
-            self._boundary["out"] = self.conv_out.weight.data.permute(0, 2, 3, 1).contiguous()
-        return self._boundary
+    def _pack(self):            # the boundary convolutions' operands
+        return {"in": ops.pack_conv_in_weight(self.conv_in.weight.data), "out": self.conv_out.weight.data.permute(0, 2, 3, 1).contiguous()}
 
     @staticmethod
     def _nhwc(r: torch.Tensor, dt) -> torch.Tensor:
@@ -549,7 +541,7 @@ class UNet2DConditionModel(nn.Module):
                 raise L.OmgHipError("added_cond_kwargs={'text_embeds','time_ids'} is required (addition_embed_type='text_time')")
             emb = self.time_embed(timestep, B, added_cond_kwargs["text_embeds"], added_cond_kwargs["time_ids"])
         ctx = _Ctx(ops.silu(emb), encoder_hidden_states.to(dt).contiguous() if encoder_hidden_states.dtype != dt or not encoder_hidden_states.is_contiguous() else encoder_hidden_states, B)
-        bw = self._boundary_weights()
+        bw = self._pk()
         x_in = sample.contiguous()
         if x_in.dtype not in (torch.float32, dt):
             x_in = x_in.to(dt)

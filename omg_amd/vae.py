@@ -23,6 +23,7 @@ from torch import nn
 
 from . import _lib as L
 from . import ops
+from ._checkpoint import PackedCache
 from .modules import Conv2d, GroupNorm, Linear
 
 
@@ -59,7 +60,7 @@ class _Resnet(nn.Module):
         return self.conv2(self.norm2(h, silu=True), residual=sc)
 
 
-class _MidAttention(nn.Module):
+class _MidAttention(PackedCache):
     def __init__(self, c, cfg, dtype, device):
         super().__init__()
         self.group_norm = GroupNorm(cfg.norm_num_groups, c, cfg.norm_eps, dtype=dtype, device=device)
@@ -67,26 +68,19 @@ class _MidAttention(nn.Module):
         self.to_k = Linear(c, c, dtype=dtype, device=device)
         self.to_v = Linear(c, c, dtype=dtype, device=device)
         self.to_out = nn.ModuleList([Linear(c, c, dtype=dtype, device=device)])
-        self._qkv = None
 
-    def _apply(self, fn, *a, **k):
-        self._qkv = None
-        return super()._apply(fn, *a, **k)
-
-    def _load_from_state_dict(self, *a, **k):
-        self._qkv = None
-        return super()._load_from_state_dict(*a, **k)
+    def _pack(self):
+        return {"w": torch.cat([self.to_q.weight.data, self.to_k.weight.data, self.to_v.weight.data]).contiguous(),
+                "b": torch.cat([self.to_q.bias.data, self.to_k.bias.data, self.to_v.bias.data]).contiguous()}
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         B, H, W, C = x.shape
         HW = H * W
         if C % 64 or HW % 8:
             raise L.OmgHipError("VAE mid attention needs C % 64 == 0 and H*W % 8 == 0")
-        if self._qkv is None:
-            self._qkv = (torch.cat([self.to_q.weight.data, self.to_k.weight.data, self.to_v.weight.data]).contiguous(),
-                         torch.cat([self.to_q.bias.data, self.to_k.bias.data, self.to_v.bias.data]).contiguous())
+        pk = self._pk()
         h = self.group_norm(x).reshape(B * HW, C)
-        qkv = ops.gemm(h, self._qkv[0], bias=self._qkv[1]).view(B, HW, 3 * C)
+        qkv = ops.gemm(h, pk["w"], bias=pk["b"]).view(B, HW, 3 * C)
         vt = ops.transpose_v(qkv[:, :, 2 * C:], C // 64, mfma_order=False)     # (B, C/64, 64, HW_pad) == V^T [C][HW_pad]
         attn = torch.empty((B * HW, C), dtype=x.dtype, device=x.device)
         scores = torch.empty((HW, HW), dtype=x.dtype, device=x.device)
@@ -136,7 +130,7 @@ class _Decoder(nn.Module):
         self.conv_out = Conv2d(rev[-1], cfg.out_channels, 3, dtype=up_dtype, device=device)    # parameters only; run by ops.conv_out
 
 
-class AutoencoderKLDecoder(nn.Module):
+class AutoencoderKLDecoder(PackedCache):
     """``decode(z)`` of diffusers' AutoencoderKL (decoder half + post_quant_conv)."""
 
     def __init__(self, cfg: Optional[VaeConfig] = None, dtype=torch.bfloat16, device="cuda", upcast: bool = False):
@@ -154,7 +148,6 @@ class AutoencoderKLDecoder(nn.Module):
         self.post_quant_conv.weight = nn.Parameter(torch.empty(c, c, 1, 1, dtype=torch.float32, device=device), requires_grad=False)
         self.post_quant_conv.bias = nn.Parameter(torch.empty(c, dtype=torch.float32, device=device), requires_grad=False)
         self.decoder = _Decoder(self.config, dtype, device, up_dtype=torch.float32 if upcast else None)
-        self._packed = {}
 
     @property
     def dtype(self):
@@ -163,14 +156,6 @@ class AutoencoderKLDecoder(nn.Module):
     @property
     def device(self):
         return self.post_quant_conv.weight.device
-
-    def _apply(self, fn, *a, **k):
-        self._packed = {}
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, *a, **k):
-        self._packed = {}
-        return super().load_state_dict(*a, **k)
 
     def init_synthetic_(self, seed: int = 0) -> "AutoencoderKLDecoder":
         g = torch.Generator(device=self.device).manual_seed(seed)
@@ -182,21 +167,24 @@ class AutoencoderKLDecoder(nn.Module):
             else:
                 w = 0.1 * torch.randn(p.shape, generator=g, device=p.device, dtype=torch.float32)
             p.data.copy_(w.to(p.dtype))
-        self._packed = {}
+        for m in self.modules():                # in-place writes: no hook saw them
+            if isinstance(m, PackedCache):
+                m.invalidate_packed()
         return self
+
+    def _pack(self):
+        d = self.decoder
+        return {"in": ops.pack_conv_in_weight(d.conv_in.weight.data), "out": d.conv_out.weight.data.permute(0, 2, 3, 1).contiguous(),
+                "pq": self.post_quant_conv.weight.data.reshape(self.config.latent_channels, -1).contiguous()}
 
     @torch.no_grad()
     def decode(self, z: torch.Tensor) -> torch.Tensor:
         """``z``: (B, 4, h, w) latents already divided by ``scaling_factor`` -> (B, 3, 8h, 8w) fp32 image in [-1, 1]-ish."""
         if not z.is_cuda:
             raise L.OmgHipError("AutoencoderKLDecoder.decode runs on the HIP kernels only (no CPU fallback)")
-        d = self.decoder
-        if "in" not in self._packed:
-            self._packed["in"] = ops.pack_conv_in_weight(d.conv_in.weight.data)
-            self._packed["out"] = d.conv_out.weight.data.permute(0, 2, 3, 1).contiguous()
-            self._packed["pq"] = self.post_quant_conv.weight.data.reshape(self.config.latent_channels, -1).contiguous()
-        x = ops.channel_mix(z.float().contiguous(), self._packed["pq"], self.post_quant_conv.bias.data)
-        x = ops.conv_in(x, self._packed["in"], d.conv_in.bias.data, self._dtype)             # NCHW fp32 -> NHWC 16-bit
+        d, pk = self.decoder, self._pk()
+        x = ops.channel_mix(z.float().contiguous(), pk["pq"], self.post_quant_conv.bias.data)
+        x = ops.conv_in(x, pk["in"], d.conv_in.bias.data, self._dtype)             # NCHW fp32 -> NHWC 16-bit
         x = d.mid_block.resnets[0](x)
         x = d.mid_block.attentions[0](x)
         x = d.mid_block.resnets[1](x)
@@ -205,7 +193,7 @@ class AutoencoderKLDecoder(nn.Module):
         for blk in d.up_blocks:
             x = blk(x)
         x = d.conv_norm_out(x, silu=True)
-        return ops.conv_out(x, self._packed["out"], d.conv_out.bias.data)
+        return ops.conv_out(x, pk["out"], d.conv_out.bias.data)
 
     @torch.no_grad()
     def decode_latents(self, latents: torch.Tensor, postprocess: bool = True) -> torch.Tensor:

@@ -105,10 +105,9 @@ def seed_encoder(model, seed):
             p.copy_(1.0 + 0.2 * r(p))
         elif leaf == "bias":
             p.copy_(0.1 * r(p))
-    model._packed = {}
-    for mod in model.modules():
-        if isinstance(mod, LiteMLA):
-            mod._packed = {}
+    for mod in model.modules():                   # in-place writes: no hook saw them
+        if hasattr(mod, "invalidate_packed"):
+            mod.invalidate_packed()
 
 
 def load_fixture(path):

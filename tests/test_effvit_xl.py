@@ -90,7 +90,7 @@ def test_folded_weights_at_eps_1e6_reproduce_every_stage_of_the_reference(fixtur
     mlas = [l for l in late.modules() if isinstance(l, LiteMLA)]
     for l in layers:
         late._pk(l)                                                   # packed at eps = 1e-5 ...
-    stale = [l._pack()["wproj"].clone() for l in mlas]
+    stale = [l._pk()["wproj"].clone() for l in mlas]
     assert late._packed and all(l._packed for l in mlas)
     sam.set_norm_eps(late, 1e-6)                                      # ... and dropped here
     assert not late._packed and not any(l._packed for l in mlas)

@@ -503,3 +503,55 @@ def test_full_width_l0_smoke(dev):
     assert np.isfinite(low).all() and np.isfinite(iou).all()
     logits = p.predict(box=np.array([100.0, 150.0, 800.0, 900.0]), multimask_output=False, return_logits=True)[0]
     assert logits.dtype == np.float32 and np.isfinite(logits).all() and np.array_equal(logits > 0, masks)
+
+
+# ------------------------------------------------------------------------------------------------ a second checkpoint into a live model
+class _Parent(torch.nn.Module):
+    def __init__(self, child):
+        super().__init__()
+        self.child = child
+
+
+def _seeded_checkpoint(cfg, seed):
+    """A checkpoint-shaped fp32 state dict of the narrow xl model (tests/test_effvit_xl.py::narrow_sam), seeded."""
+    from omg_amd.efficientvit import EfficientViTSamImageEncoder
+    enc = EfficientViTSamImageEncoder(cfg, dtype=torch.float32, device="cpu")
+    seed_encoder(enc, seed)
+    pe, md = st.build((64, 64), (128, 128), mlp_dim=128)
+    sd = {"child.image_encoder." + k: v.clone() for k, v in enc.state_dict().items()}
+    sd.update({"child.prompt_encoder." + k: v for k, v in st.seed_state(pe, seed + 1).state_dict().items()})
+    sd.update({"child.mask_decoder." + k: v for k, v in st.seed_state(md, seed + 2).state_dict().items()})
+    return sd
+
+
+def test_a_second_checkpoint_loaded_through_a_parent_replaces_every_derived_operand(dev):
+    """Load A through a parent module, run, load B through the parent, run again: masks, IoU predictions and the dense positional encoding
+    are the bits of a model that only ever saw B — the same kernels on the same operands.  ``nn.Module.load_state_dict`` on a parent
+    calls no child's ``load_state_dict``; packed weights kept from A (BatchNorm folds of the encoder, the decoder's transposed-convolution
+    operands, the positional encoding of A's Gaussian matrix) would show here."""
+    from tests.effvit_xl_torch import load_fixture_xl
+    from tests.test_effvit_xl import narrow_sam
+    cfg = load_fixture_xl()[1]
+    sd_a, sd_b = _seeded_checkpoint(cfg, 11), _seeded_checkpoint(cfg, 23)
+    image = np.random.RandomState(5).randint(0, 256, (96, 128, 3)).astype(np.uint8)
+    box = torch.tensor([[20.0, 10.0, 100.0, 80.0]], device=dev)
+
+    def run(model):
+        p = sam.EfficientViTSamPredictor(model)
+        p.set_image(image)
+        masks, iou, _ = p.predict_torch(point_coords=None, point_labels=None, boxes=box, multimask_output=False, return_logits=True)
+        return masks, iou, model.prompt_encoder.get_dense_pe()
+
+    live = _Parent(narrow_sam(cfg, torch.float16).to(dev))
+    live.load_state_dict(sd_a, strict=True)
+    first = run(live.child)
+    live.load_state_dict(sd_b, strict=True)
+    second = run(live.child)
+    fresh = _Parent(narrow_sam(cfg, torch.float16).to(dev))
+    fresh.load_state_dict(sd_b, strict=True)
+    want = run(fresh.child)
+    assert all(torch.isfinite(t.float()).all() for t in want)
+    for name, a, w in zip(("masks", "iou", "dense_pe"), first, want):
+        assert not torch.equal(a, w), f"{name}: checkpoints A and B do not tell apart"
+    for name, g, w in zip(("masks", "iou", "dense_pe"), second, want):
+        assert torch.equal(g, w), f"{name} after the reload differs from a model that only saw B"

@@ -81,11 +81,11 @@ def aggreg_ab(lines, dev, calls):
             with torch.no_grad():
                 for p in m.parameters():
                     p.copy_(torch.randn(p.shape, generator=g, device=dev) * 0.1)
-            m._packed = {}
+            m.invalidate_packed()
             mods[aggreg] = m
         T3, M = 3 * c, side * side
         buf = (torch.randn(M, 2 * T3, device=dev, generator=torch.Generator(device=dev).manual_seed(1))).half()
-        pg, pf = mods["gemm"]._pack(), mods["fused"]._pack()
+        pg, pf = mods["gemm"]._pk(), mods["fused"]._pk()
 
         def run_gemm():
             t = ops.dwconv2d(buf[:, :T3], pg["taps"][0], 1, side, side, 3)
