@@ -88,6 +88,18 @@ typedef struct {
 
 int omg_gemm(const omg_gemm_args* a, void* stream);
 
+/* The buffer-descriptor offset limit of the GEMM family, in bytes (host-only query, no GPU needed).
+ *
+ * The large-tile kernels behind omg_gemm, omg_conv2d, omg_conv2d_slots, omg_gemm_mx8 and omg_conv2d_mx8 reach every operand through
+ * a buffer descriptor and a 32-bit byte offset.  They are used while the byte extent of EVERY operand — rows x leading dimension
+ * x element size for A, W, C, the residual and the per-sample bias table; B*Hin*Win*C for an NHWC input; 4x the phase launch's rows
+ * for the Y of upsample == 2; the scale arrays of the MX-fp8 entries — is BELOW this limit.
+ *   - Below the limit: any tile kernel may run; all of them give the same bits.
+ *   - At or beyond it: the 16-bit entries (omg_gemm, omg_conv2d, omg_conv2d_slots, upsample == 2 included) run their 128x128 kernel,
+ *     which forms 64-bit addresses — the same bits again, for operands of any size the int32 row count allows.  The MX-fp8 entries
+ *     (omg_gemm_mx8, omg_conv2d_mx8) have no such kernel: they return OMG_EINVAL and write nothing. */
+int64_t omg_debug_gemm_offset_limit(void);
+
 /* ------------------------------------------------------------------------
  * omg_quant_mx8 / omg_gemm_mx8 — the same Linear layers with OCP MX fp8
  * operands (BASELINE.json north_star "MFMA bf16/fp8", configs[4]): elements

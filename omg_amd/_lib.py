@@ -246,6 +246,7 @@ SYMBOLS = {
     "omg_debug_set_glds": (None, [c_i32]),
     "omg_debug_set_gemm_variant": (None, [c_i32]),
     "omg_debug_choose_variant": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
+    "omg_debug_gemm_offset_limit": (c_i64, []),
     "omg_debug_set_mx8_split": (None, [c_i32]),
     "omg_debug_set_attn_variant": (None, [c_i32]),
 }

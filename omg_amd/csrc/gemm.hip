@@ -785,8 +785,8 @@ int launch(const GemmP& p, hipStream_t s) {
   const int mrows = p.tile_groups > 1 ? p.rows_per_group : p.M;
   if (g_use_glds) {
     int v = choose_variant(mrows, p.tile_groups, p.N, CONV, p.act == OMG_ACT_GEGLU);
-    // v6 (interleaved DMA) handles everything except the LoRA second K-segment and > 2 GiB operands
-    const long lim = 0x7fff0000L;
+    // v6 (interleaved DMA) handles everything except the LoRA second K-segment and operands that reach GEMM_OFFSET_LIMIT (gemm_epilogue.h)
+    const long lim = GEMM_OFFSET_LIMIT;
     const long a_sz = CONV ? (long)p.M / (p.Hout * p.Wout) * p.Hin * p.Win * (p.C1 > p.C2 ? p.C1 : p.C2) * 2 : (long)p.M * p.lda * 2;
     const long c_sz = (long)p.M * (p.ldc > p.ldr ? p.ldc : p.ldr) * 2;
     const bool v6ok = p.K2 == 0 && p.A2 == nullptr && p.K % 64 == 0 && a_sz < lim && (long)p.N * p.ldw * 2 < lim && c_sz < lim &&
@@ -837,13 +837,13 @@ int launch(const GemmP& p, hipStream_t s) {
 }
 
 // One phase of omg_conv2d's upsample == 2 form.  Two kernels only: the 256x320 tile where the chooser picks it, the 128x128 kernel for
-// everything else (small and ragged shapes, operands >= 2 GiB) — both give the same bits, so the choice never shows in a result.
+// everything else (small and ragged shapes, operands that reach GEMM_OFFSET_LIMIT) — both give the same bits, so the choice never shows in a result.
 template <typename T>
 int launch_phase(const GemmP& p, hipStream_t s) {
   const int mrows = p.tile_groups > 1 ? p.rows_per_group : p.M;
   if (g_use_glds) {
     const int v = choose_variant(mrows, p.tile_groups, p.N, true);
-    const long lim = 0x7fff0000L;
+    const long lim = GEMM_OFFSET_LIMIT;
     const long a_sz = (long)p.M * p.C1 * 2, c_sz = 4L * p.M * p.ldc * 2;
     const bool ok = a_sz < lim && (long)p.N * p.ldw * 2 < lim && c_sz < lim &&
                     (p.group_bias == nullptr || (long)(p.M / p.rows_per_group + 1) * p.ldgb * 2 < lim);
@@ -899,6 +899,8 @@ extern "C" int omg_debug_choose_variant(int mrows, int groups, int N, int conv) 
   g_variant = saved;
   return v;
 }
+// host-only: GEMM_OFFSET_LIMIT (gemm_epilogue.h) — an operand whose byte extent reaches it leaves the buffer-descriptor kernels
+extern "C" int64_t omg_debug_gemm_offset_limit(void) { return GEMM_OFFSET_LIMIT; }
 
 extern "C" int omg_gemm(const omg_gemm_args* a, void* stream) {
   OMG_REQUIRE(a != nullptr, "omg_gemm: null args");

@@ -78,13 +78,26 @@ OMG_DEV void swap_runs(unsigned (&q)[4]) {   // q[0..1] = run 0 (4 halves), q[2.
 // makes a load return zeros and a store vanish, so row / column predicates are a v_cndmask on the offset instead of an
 // exec-mask branch around every access, and there is no 64-bit address arithmetic per access.
 constexpr int EPI_OOB = 0x7f000000;
+// num_records of an epilogue descriptor (C / Y, residual, per-sample bias) never exceeds EPI_CLAMP, so that EPI_OOB — alone, OR-ed with a
+// row offset or with a column constant added — is out of range for every one of them.
+constexpr long EPI_CLAMP = 0x7effff00L;
+// The largest byte extent (rows x leading dimension x element size, as the launch gates compute it) of ANY operand the buffer-descriptor
+// kernels address correctly (v6, v7, v12, v13 and the MX-fp8 kernels; per-operand table in DESIGN.md, "The 2 GiB operand edge").  The
+// epilogue operands set it: beyond EPI_CLAMP their stores vanish and their loads read zeros.  A / X1 / X2 / W and the MX scale arrays reach
+// further (int offsets, descriptors clamped at or cast below 2^31) and share the one gate.  An operand whose extent is not BELOW the limit
+// takes the 128x128 kernel's 64-bit pointers (omg_gemm, omg_conv2d, omg_conv2d_slots) or is refused (omg_gemm_mx8, omg_conv2d_mx8).
+constexpr long GEMM_OFFSET_LIMIT = EPI_CLAMP;
+static_assert(EPI_CLAMP <= (long)EPI_OOB, "the out-of-range sentinel must lie at or beyond num_records of every epilogue descriptor");
+static_assert(GEMM_OFFSET_LIMIT <= EPI_CLAMP, "an epilogue operand the gate admits must fit inside its clamped descriptor");
+static_assert((long)EPI_OOB + GEMM_OFFSET_LIMIT <= 0xffffffffL, "sentinel + any admitted offset must not wrap round the 32-bit offset into range");
+static_assert(GEMM_OFFSET_LIMIT <= 0x7fffff00L, "the A / X descriptors are clamped at 0x7fffff00 and their sentinel is 0x7ffffff0");
 // The descriptor words go through readfirstlane: built from kernel arguments they ARE wave-uniform, but hipcc kept them in VGPRs
 // inside the epilogue and wrapped EVERY buffer load / store in a waterfall loop (4 v_readfirstlane + compare + saveexec + branch:
 // ~900 loops in a v7 kernel, the 32 stores of a wave serialised one loop after the other — cdna guide T20).
 OMG_DEV __amdgpu_buffer_rsrc_t epi_rsrc(const char* base, long bytes) {
   const unsigned long long a = (unsigned long long)base;
   const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-  const int n = __builtin_amdgcn_readfirstlane(base != nullptr ? (int)(bytes < 0x7effff00L ? bytes : 0x7effff00L) : 0);
+  const int n = __builtin_amdgcn_readfirstlane(base != nullptr ? (int)(bytes < EPI_CLAMP ? bytes : EPI_CLAMP) : 0);
   return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)hi << 32) | lo), 0, n, 0x00020000);
 }
 // 16 bytes at byte offset `off` (this lane's 8 consecutive columns) -> the 8 values in accumulator order (runs 0, 1)
@@ -371,7 +384,7 @@ OMG_DEV void epilogue_direct(const GemmP& p, f32x16 (&acc)[MT][NT], int lane, in
   cx.hi = lane >> 5; cx.l31 = lane & 31; cx.wm0 = wm0; cx.m_end = m_end;
   cx.rsC = epi_rsrc(p.C, p.QS != nullptr ? (long)(p.M - 1) * p.ldc + n_out : ((long)(p.M - 1) * p.ldc + n_out) * 2);
   cx.rsR = epi_rsrc(p.residual, ((long)(p.M - 1) * p.ldr + p.N) * 2);
-  cx.rsG = epi_rsrc(has_gb ? p.group_bias : nullptr, 0x7effff00L);
+  cx.rsG = epi_rsrc(has_gb ? p.group_bias : nullptr, EPI_CLAMP);
   // the buffer bound only protects the end of the matrix, not the end of a row: per-unit column predicate, as an
   // offset bit pattern that is OR-ed in (row offsets stay far below EPI_OOB's bits)
 #pragma unroll

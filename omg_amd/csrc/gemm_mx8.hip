@@ -657,9 +657,9 @@ extern "C" int omg_gemm_mx8(const omg_gemm_mx8_args* a, void* stream) {
   OMG_REQUIRE(a->groups >= 1 && (long)a->groups * a->rows_per_group == a->M, "omg_gemm_mx8: M != groups*rows_per_group");
   if (a->act == OMG_ACT_GEGLU) OMG_REQUIRE(a->N % 64 == 0 && !a->residual, "omg_gemm_mx8: GEGLU needs N % 64 == 0, no residual");
   if (a->residual) OMG_REQUIRE(a->ldr % 8 == 0, "omg_gemm_mx8: ldr");
-  const long lim = 0x7fff0000L;
+  const long lim = GEMM_OFFSET_LIMIT;      // no 64-bit kernel behind these entries: beyond the limit the call is refused
   OMG_REQUIRE((long)a->M * a->lda < lim && (long)a->N * a->ldw < lim && (long)a->M * a->ldc * c_elt < lim && (long)a->M * a->ldr * 2 < lim,
-              "omg_gemm_mx8: an operand exceeds the 2 GiB buffer-descriptor range");
+              "omg_gemm_mx8: an operand reaches the buffer-descriptor offset limit (omg_debug_gemm_offset_limit)");
   GemmP p{};
   p.M = a->M; p.N = a->N; p.K = a->K;
   p.A = (const char*)a->A; p.lda = a->lda; p.W = (const char*)a->W; p.ldw = a->ldw;
@@ -692,9 +692,9 @@ extern "C" int omg_conv2d_mx8(const omg_conv2d_mx8_args* a, void* stream) {
   const long M = (long)a->B * a->H * a->W;
   if (M == 0) return OMG_OK;
   const long K = 9L * a->Cin;
-  const long lim = 0x7fff0000L;
+  const long lim = GEMM_OFFSET_LIMIT;      // no 64-bit kernel behind these entries: beyond the limit the call is refused
   OMG_REQUIRE(M * a->Cin < lim && (long)a->Cout * K < lim && M * a->Cout * 2 < lim && (long)(a->Cin / 128) * M * 4 < lim,
-              "omg_conv2d_mx8: an operand exceeds the 2 GiB buffer-descriptor range");
+              "omg_conv2d_mx8: an operand reaches the buffer-descriptor offset limit (omg_debug_gemm_offset_limit)");
   GemmP p{};
   p.M = (int)M; p.N = a->Cout; p.K = (int)K;
   p.A = (const char*)a->X; p.lda = a->Cin; p.W = (const char*)a->Wq; p.ldw = K;

@@ -162,7 +162,7 @@ OMG_DEV void epilogue13(const GemmP& p, f32x16 (&acc)[4][5], int lane, int wm0, 
   if constexpr (PH) cx.rsC = epi_rsrc(p.C, ((4L * p.M - 1) * p.ldc + p.N) * 2);      // a phase launch scatters its M rows over the 4 M rows of the output
   else cx.rsC = epi_rsrc(p.C, ((long)(p.M - 1) * p.ldc + p.N) * 2);
   cx.rsR = epi_rsrc(p.residual, ((long)(p.M - 1) * p.ldr + p.N) * 2);
-  cx.rsG = epi_rsrc(has_gb ? p.group_bias : nullptr, 0x7effff00L);
+  cx.rsG = epi_rsrc(has_gb ? p.group_bias : nullptr, EPI_CLAMP);
 #pragma unroll
   for (int j = 0; j < 5; ++j)
 #pragma unroll
