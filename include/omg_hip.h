@@ -112,8 +112,15 @@ int64_t omg_debug_gemm_offset_limit(void);
  *
  * omg_quant_mx8: X[M,K] (fp16 / bf16, row stride ldx elements) -> Q[M,K]
  * bytes (row stride ldq) + S.  Scale = smallest power of two with
- * amax / scale <= 448 (no element saturates).  K % 128 == 0, s_ld >= M.
+ * amax / scale <= 448 (no element saturates), clamped at 2^-127 (byte 0, also
+ * the byte of a block of zeros).  K % 128 == 0, s_ld >= M.
  * Weights are quantised once with the same call (rows = output features).
+ * Non-finite input (this and every other producer of the format):
+ *  - A non-finite input element is stored as an e4m3 NaN byte (0x7f or 0xff).
+ *  - Every block of the tensor that holds no non-finite element has exactly
+ *    the bytes and scale byte it would have without it.
+ *  - Within the affected block, the finite elements and the scale byte are
+ *    unspecified.  The row's dot product is NaN regardless.
  * ---------------------------------------------------------------------- */
 int omg_quant_mx8(int32_t dtype, const void* x, int64_t ldx, int32_t M, int32_t K,
                   void* q, int64_t ldq, void* scales, int32_t s_ld, void* stream);

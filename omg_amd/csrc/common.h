@@ -66,16 +66,19 @@ OMG_DEV float silu_fast(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __exp
 #include "gelu.h"         // gelu_f / gelu_f2: the exact (erf) GELU of the GEGLU epilogues through one transcendental
 
 // ---- MX-fp8 quantisation helpers (gemm_mx8.hip, norm.hip): E8M0 scale of a 32-block and the e4m3 element cast.
-// Scale = the smallest power of two 2^e with amax / 2^e <= 448 (the e4m3 maximum): no element saturates.  Returns e + 127.
+// Scale = the smallest power of two 2^e with amax / 2^e <= 448 (the e4m3 maximum), clamped at 2^-127: no element saturates.
+// Returns e + 127.  448 = 1.75 * 2^8, so amax = m * 2^E (1 <= m < 2) has e = E - 8, one more where m > 1.75: read off amax's own
+// exponent and mantissa fields, with no product that could be an fp32 subnormal (amax * (1 / 448) was one for amax < 448 * 2^-126,
+// and its exponent field 0 gave byte 1 where the clamp says 0).  A subnormal amax (field 0) and a block of zeros get byte 0.
+// Non-finite input (contract: oracle/mx8.py): fmaxf drops a NaN, which the element cast then stores as a NaN byte; an infinite
+// amax gets byte 254, whose inverse below is 0.0, so that inf * 0 = NaN whatever the cast does with an infinity.
 OMG_DEV unsigned mx8_scale_exp(float amax) {
-  const float v = amax * (1.0f / 448.0f);
-  const unsigned bits = __builtin_bit_cast(unsigned, v);
-  int e = (int)(bits >> 23) - 127 + ((bits & 0x7fffffu) != 0 ? 1 : 0);
-  e = e < -127 ? -127 : (e > 127 ? 127 : e);
-  return (unsigned)(e + 127);
+  const unsigned bits = __builtin_bit_cast(unsigned, amax);
+  const unsigned be = (bits >> 23) + ((bits & 0x7fffffu) > 0x600000u ? 1u : 0u);
+  return bits >= 0x7f800000u ? 254u : (be > 8u ? be - 8u : 0u);
 }
-// 2^-(be - 127): be = 0 -> 2^127 (a block of zeros), be = 254 -> 2^-127 as the exponent field 0 would be 0.0, never reached by
-// fp16 / bf16 inputs (|x| / 448 < 2^127)
+// 2^-(be - 127): be = 0 -> 2^127 (a block of zeros or of tiny values), be = 254 -> exponent field 0 = 0.0 instead of 2^-127:
+// finite fp16 / bf16 inputs stay below byte 248, only an infinite amax gets 254 (see above)
 OMG_DEV float mx8_inv_scale(unsigned be) { return __builtin_bit_cast(float, (254u - be) << 23); }
 OMG_DEV unsigned mx8_pack4(float a, float b, float c, float d) {     // four e4m3 bytes, round to nearest even (v_cvt_pk_fp8_f32: OCP on gfx950)
   int r = 0;

@@ -530,7 +530,12 @@ __global__ __launch_bounds__(256, 1) void gemm_mx8_kernel_p(GemmP p) {
 // ------------------------------------------------------------------------------------------------
 // Quantiser: X[M, K] (fp16 / bf16, row stride ldx) -> Q[M, K] e4m3 bytes (row stride ldq) + S[K/128][s_ld] scale dwords.
 // Scale of a 32-block: the smallest power of two 2^e with amax / 2^e <= 448 (the e4m3 maximum), stored as E8M0 e + 127 —
-// no element saturates, the largest keeps all three mantissa bits.  A block of zeros gets byte 0 (2^-127).
+// no element saturates, the largest keeps all three mantissa bits.  The exponent is clamped at -127: a block of zeros, and one
+// whose amax is at most 448 * 2^-127, gets byte 0.
+// Non-finite input:
+//  * A non-finite input element is stored as an e4m3 NaN byte (0x7f or 0xff).
+//  * Every block of the tensor that holds no non-finite element has exactly the bytes and scale byte it would have without it.
+//  * Within the affected block, the finite elements and the scale byte are unspecified.  The row's dot product is NaN regardless.
 // A workgroup takes 32 rows; per iteration one 128-wide stage: thread t -> row t / 8, elements 16 (t % 8) .. + 15, so two
 // neighbouring lanes share a 32-block (one DPP exchange for the amax), a row's 128 output bytes are one whole cache line and
 // the 32 rows' scale dwords of the stage are one more.

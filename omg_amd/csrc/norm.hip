@@ -100,8 +100,8 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(GnP p) {
             if (sc_mode == 2) { if ((vec & 15) == 0) *(unsigned*)(p.S + (((long)(vec >> 4) * p.P + gp) << 2)) = sc4; }
             else if (sc_mode == 1) { if ((vec & 7) == 0) *(unsigned short*)(p.S + (((long)(vec >> 4) * p.P + gp) << 2) + ((vec >> 2) & 3)) = (unsigned short)sc4; }
             else if ((vec & 3) == 0) p.S[(((long)(vec >> 4) * p.P + gp) << 2) + ((vec >> 2) & 3)] = (unsigned char)be;
-            const int cpad = C + vec * 8;      // the first (Cq - C) / 8 lanes of the pixel also clear its pad channels
-            if (cpad < p.Cq) {
+            // the pixel's lanes also clear its pad channels: lane vec takes C + 8 vec, and C = 32 (96 pad channels, four lanes) two more
+            for (int cpad = C + vec * 8; cpad < p.Cq; cpad += C) {
               *(u32x2*)(p.Q + gp * p.Cq + cpad) = u32x2{0u, 0u};
               if ((cpad & 31) == 0) p.S[(((long)(cpad >> 7) * p.P + gp) << 2) + ((cpad >> 5) & 3)] = 0;
             }

@@ -214,9 +214,12 @@ def gemm_mx8(a: Mx8Tensor, w: Mx8Tensor, *, out_dtype: torch.dtype = torch.float
     n_out = N // 2 if act == L.ACT_GEGLU else N
     oq = None
     if out_mx8:
-        assert out is None and act == L.ACT_GEGLU and N % 256 == 0
-        oq = Mx8Tensor(torch.empty((M, n_out), dtype=torch.uint8, device=a.q.device),
-                       torch.empty((n_out // 128, (M + 3) // 4 * 4), dtype=torch.int32, device=a.q.device), tuple(a.shape[:-1]) + (n_out,))
+        assert act == L.ACT_GEGLU and N % 256 == 0
+        oq = out        # a caller's Mx8Tensor (any row stride % 16, any scale stride >= M, % 4), as quant_mx8 takes one
+        if oq is None:
+            oq = Mx8Tensor(torch.empty((M, n_out), dtype=torch.uint8, device=a.q.device),
+                           torch.empty((n_out // 128, (M + 3) // 4 * 4), dtype=torch.int32, device=a.q.device), tuple(a.shape[:-1]) + (n_out,))
+        assert isinstance(oq, Mx8Tensor) and oq.scales.shape[0] == n_out // 128
         out = oq.q
     elif out is None:
         out = torch.empty((M, n_out), dtype=out_dtype, device=a.q.device)

@@ -395,3 +395,25 @@ def test_geglu_epilogue_mx8_output_equals_quantising_the_16bit_result(dev, dtype
     assert fused.q.shape == (M, N // 2) and fused.shape == (M, N // 2)
     assert torch.equal(fused.q, two.q), f"{(fused.q != two.q).sum().item()} bytes differ"
     assert torch.equal(fused.scales[:, :M], two.scales[:, :M])
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+def test_geglu_epilogue_mx8_output_ragged_rows_padded_scale_stride_canaries(dev, dtype):
+    """The same statement with ragged M (300: no multiple of the 256-row tile), a scale stride above M (sc_ld = 304) and
+    canary-filled outputs with guard rows: nothing outside q[M, N/2] and scales[N/2/128, M] may change."""
+    M, N, K = 300, 1024, 384
+    a = gen((M, K), 41, dtype=dtype).to(dev)
+    w = gen((N, K), 42, scale=K ** -0.5, dtype=dtype).to(dev)
+    b = gen((N,), 43, dtype=dtype).to(dev)
+    ta, tw = ops.quant_mx8(a), ops.quant_mx8(w)
+    kw = dict(bias=b, act=L.ACT_GEGLU, out_dtype=dtype)
+    two = ops.quant_mx8(ops.gemm_mx8(ta, tw, **kw))
+    n_out, sc_ld, canary, canary32 = N // 2, M + 4, 0xA5, -1515870811       # 0xA5A5A5A5
+    qb = torch.full((M + 2, n_out), canary, dtype=torch.uint8, device=dev)
+    sb = torch.full((n_out // 128 + 2, sc_ld), canary32, dtype=torch.int32, device=dev)
+    fused = ops.gemm_mx8(ta, tw, out_mx8=True, out=ops.Mx8Tensor(qb[1:M + 1], sb[1:-1]), **kw)
+    assert fused.scales.stride(0) == sc_ld and fused.q.data_ptr() == qb.data_ptr() + n_out
+    assert torch.equal(fused.q, two.q), f"{(fused.q != two.q).sum().item()} bytes differ"
+    assert torch.equal(fused.scales[:, :M], two.scales[:, :M])
+    assert (qb[0] == canary).all() and (qb[M + 1] == canary).all(), "bytes outside q[M, N/2] were written"
+    assert (sb[0] == canary32).all() and (sb[-1] == canary32).all() and (sb[:, M:] == canary32).all(), "dwords outside scales[N/2/128, M] were written"
