@@ -917,6 +917,26 @@ int omg_canny_nms(int B, int H, int W, int C, const uint8_t* image, int low, int
 int64_t omg_canny_hysteresis_ws_bytes(int B, int H, int W);
 int omg_canny_hysteresis(int B, int H, int W, const uint8_t* state, void* workspace, int out_form, int out_dtype, void* out, void* stream);
 
+/* ------------------------------------------------------------------------
+ * TOOLS AND TESTS ONLY — not part of the product path and no promise of stability.  Process-wide switches
+ * (not thread-safe; set them while no call is in flight) and host-side queries of tools/ and tests/.  omg_debug_gemm_offset_limit
+ * is declared above, with the GEMM family it describes.
+ *   omg_debug_set_glds: 0 = the register-staged build of the 128x128 GEMM kernel instead of its LDS-DMA one; anything else = default.
+ *   omg_debug_set_gemm_variant: bits 0-7 force one GEMM tile configuration (0 = the cost model chooses), the bits above are debug bits
+ *     of the chosen kernel (tools/).  omg_debug_choose_variant: host-only, the configuration the cost model picks for (rows per group,
+ *     groups, N, conv bit 0: a convolution, bit 1: a GEGLU epilogue).
+ *   omg_debug_read_ts: copies the block timestamps that debug bit 16 of the large-tile GEMM kernels leaves (6 per block, at most 8192
+ *     blocks) to the HOST buffer `out`; returns the hipError_t of the copy.
+ *   omg_debug_set_mx8_split: the MX-fp8 GEMM's DMA split | debug bits << 8.
+ *   omg_debug_set_attn_variant: bits 0-7 force one attention kernel (0 = the heuristic), the bits above are debug bits.
+ * ---------------------------------------------------------------------- */
+void omg_debug_set_glds(int on);
+void omg_debug_set_gemm_variant(int v);
+int omg_debug_choose_variant(int mrows, int groups, int N, int conv);
+int omg_debug_read_ts(long long* out, int blocks);
+void omg_debug_set_mx8_split(int d1);
+void omg_debug_set_attn_variant(int v);
+
 #ifdef __cplusplus
 }
 #endif

@@ -226,12 +226,3 @@ def test_from_pretrained_maps_a_dpm_scheduler_config(tmp_path):
     json.dump(dict(cfg, algorithm_type="sde-dpmsolver++"), open(os.path.join(other, "scheduler", "scheduler_config.json"), "w"))
     with pytest.raises(L.OmgHipError, match="algorithm_type"):
         compat.LoraMultiConceptPipeline.from_pretrained(other, torch_dtype=torch.float16, variant="fp16")
-
-
-def test_abi_exports_the_multistep_step():
-    import subprocess
-    assert "omg_fuse_cfg_step_ms" in L.SYMBOLS
-    lib = L.lib()
-    assert hasattr(lib, "omg_fuse_cfg_step_ms") and lib.omg_abi_version() == 6
-    nm = subprocess.run(["nm", "-D", "--defined-only", L.LIB_PATH], capture_output=True, text=True).stdout
-    assert " T omg_fuse_cfg_step_ms\n" in nm

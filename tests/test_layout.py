@@ -23,28 +23,95 @@ def test_library_exports_every_declared_symbol():
     lib = _lib.lib()                       # raises if libomg_hip.so is missing or stale
     declared = header_symbols()
     assert len(declared) >= 18
+    assert declared == sorted(_lib.SYMBOLS), "the bindings are the header's prototypes, no more and no fewer"
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in include/omg_hip.h but not exported"
-        assert name in _lib.SYMBOLS, f"{name} has no ctypes prototype in omg_amd/_lib.py"
     nm = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
     for name in declared:
         assert re.search(rf"\bT {name}\b", nm), f"{name} is not a defined text symbol"
-    assert lib.omg_abi_version() == 6
+    for name in re.findall(r"\bT (omg_\w+)$", nm, flags=re.M):
+        assert name in declared, f"{name} is exported but include/omg_hip.h does not declare it"
+    assert lib.omg_abi_version() == 6 == _lib.OMG_ABI_VERSION
 
 
-def test_struct_sizes_match_the_header():
-    """ctypes mirrors must have the size the C compiler gives the structs."""
-    import ctypes
-    from omg_amd import _lib
-    code = '#include <stdio.h>\n#include "omg_hip.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu %zu\\n",sizeof(omg_gemm_args),sizeof(omg_conv2d_args),sizeof(omg_attn_args),sizeof(omg_step_args),sizeof(omg_gemm_mx8_args),sizeof(omg_conv2d_mx8_args),sizeof(omg_conv2d_f32_args));return 0;}'
-    exe = os.path.join(ROOT, "tests", "_sizes.out")
-    subprocess.run(["gcc", "-x", "c", "-I", os.path.join(ROOT, "include"), "-o", exe, "-"], input=code.encode(), check=True)
+def c_layout(header_dir, structs):
+    """{struct: [sizeof, (offsetof, sizeof) of every field ...]} as gcc lays them out, from ONE compiled program."""
+    lines = []
+    for name, cls in structs.items():
+        lines.append(f'printf("{name} %zu", sizeof({name}));')
+        lines += [f'printf(" %zu %zu", offsetof({name}, {f}), sizeof((({name}*)0)->{f}));' for f, _ in cls._fields_]
+        lines.append('printf("\\n");')
+    code = '#include <stdio.h>\n#include <stddef.h>\n#include "omg_hip.h"\nint main(){\n' + "\n".join(lines) + "\nreturn 0;}\n"
+    exe = os.path.join(ROOT, "tests", "_layout.out")
+    subprocess.run(["gcc", "-x", "c", "-I", header_dir, "-o", exe, "-"], input=code.encode(), check=True)
     try:
-        out = subprocess.check_output([exe], text=True).split()
+        out = subprocess.check_output([exe], text=True)
     finally:
         os.remove(exe)
-    got = [ctypes.sizeof(c) for c in (_lib.GemmArgs, _lib.Conv2dArgs, _lib.AttnArgs, _lib.StepArgs, _lib.GemmMx8Args, _lib.Conv2dMx8Args, _lib.Conv2dF32Args)]
-    assert got == [int(v) for v in out]
+    return {row[0]: [int(v) for v in row[1:]] for row in (line.split() for line in out.splitlines())}
+
+
+def test_struct_layouts_match_the_header():
+    """Every generated ctypes.Structure has the size, and every field the offset and size, that the C compiler gives the header's struct."""
+    import ctypes
+    from omg_amd import _lib
+    assert len(_lib.STRUCTS) >= 13
+    want = c_layout(os.path.join(ROOT, "include"), _lib.STRUCTS)
+    assert sorted(want) == sorted(_lib.STRUCTS)
+    for name, cls in _lib.STRUCTS.items():
+        got = [ctypes.sizeof(cls)]
+        for f, _ in cls._fields_:
+            got += [getattr(cls, f).offset, getattr(cls, f).size]
+        assert got == want[name], name
+
+
+SYNTHETIC = """
+/* a comment with int omg_not_a_prototype(void); inside */
+#ifndef T_H
+#define T_H
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define T_N 3
+enum { T_A = 0, T_B = -2 };
+typedef struct { int32_t a; const void* p; float f[T_N], g; } t_inner;
+typedef struct { uint8_t tag; t_inner in[2]; int64_t n; const t_inner* q; } t_outer;
+const char* omg_name(void);
+void omg_set(int v);
+int64_t omg_run(const t_outer* a, const int32_t* idx, long long* ts, float s, void* stream);
+#ifdef __cplusplus
+}
+#endif
+#endif
+"""
+
+
+def test_the_header_parser_on_synthetic_text():
+    import ctypes
+    from omg_amd import _lib
+    structs, symbols, consts = _lib.parse_header(SYNTHETIC)
+    assert consts == {"T_N": 3, "T_A": 0, "T_B": -2}                       # the include guard defines no value
+    inner, outer = structs["t_inner"], structs["t_outer"]
+    assert [f for f, _ in inner._fields_] == ["a", "p", "f", "g"] and [f for f, _ in outer._fields_] == ["tag", "in", "n", "q"]
+    assert ctypes.sizeof(inner) == 32 and inner.f.offset == 16 and inner.f.size == 12 and inner.g.offset == 28      # array sized by the #define
+    assert ctypes.sizeof(outer) == 88 and getattr(outer, "in").offset == 8 and outer.n.offset == 72                 # nested by value, 8-aligned
+    assert outer.q.size == 8 and dict(outer._fields_)["q"] is ctypes.c_void_p
+    assert symbols == {"omg_name": (ctypes.c_char_p, []), "omg_set": (None, [ctypes.c_int32]),
+                       "omg_run": (ctypes.c_int64, [ctypes.POINTER(outer), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p])}
+    bad = {"unknown type 'double'": "int omg_f(double x);",
+           "unknown type 'size_t'": "typedef struct { size_t n; } t_s;",
+           "unknown type 't_later\\*'": "int omg_f(const t_later* a);",
+           "unknown return type 'void\\*'": "void* omg_f(int x);",
+           "not understood: 'typedef union": "typedef union { int a; float b; } t_u;",
+           "not understood: 'int omg_f": "int omg_f(int (*cb)(int));",
+           "unknown type 'int a :'": "typedef struct { int a : 3; } t_b;",
+           "not understood: '#if T_N": "#if T_N > 2\nint omg_f(void);\n#endif",
+           "not understood: 'static int x": "int omg_f(void);\nstatic int x;",
+           "not an integer constant: 'T_MISSING'": "typedef struct { int a[T_MISSING]; } t_a;"}
+    for message, text in bad.items():
+        with pytest.raises(_lib.OmgHipError, match=message):
+            _lib.parse_header(text)
 
 
 def test_product_never_imports_the_oracle():

@@ -9,8 +9,6 @@ from omg_amd import ops, _lib as L
 M, N, K = (int(a) for a in sys.argv[1:4]) if len(sys.argv) > 3 else (32768, 10240, 1280)
 extra = int(sys.argv[4]) if len(sys.argv) > 4 else 0
 lib = L.lib()
-lib.omg_debug_read_ts.restype = ctypes.c_int
-lib.omg_debug_read_ts.argtypes = [ctypes.c_void_p, ctypes.c_int]
 dev = torch.device("cuda:0")
 x = torch.randn(M, K, device=dev, dtype=torch.float16)
 w = torch.randn(N, K, device=dev, dtype=torch.float16)
